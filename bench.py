@@ -4,12 +4,15 @@
 
     python bench.py [--gpus N --steps K --warmup W]        # N=1: one process
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+    python bench.py ... --dump-outputs DIR                 # + the last timed step's k, P(k), mode counts as DIR/*.npy
+    python bench.py ... --full                             # + streaming ceiling, other legs, bispectrum, kappa, CPU baselines
 
 One "step" = zero the grid, paint all particles, forward FFT, shell-bin P(k).
 N=1 workload: 1024^3 synthetic lattice+Gaussian particles on a
 1024^3 grid, fp32.  N>1: the same 1024^3 problem slab-decomposed along axis 0
 (strong scaling; one RCCL all-to-all per step for the slab transpose).
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times K steps and prints the line;
+everything else it can measure runs with --full (or with its own switch: --legs, --bispec, --kappa, --cpu-sample).
 """
 import argparse
 import json
@@ -39,14 +42,37 @@ def parse():
     ap.add_argument("--dtype", default="f32", choices=["f32", "f64"])
     ap.add_argument("--order", default="natural", choices=["natural", "shuffled"])
     ap.add_argument("--method", default="auto", choices=["auto", "tiled", "tiled2", "direct"])
-    ap.add_argument("--cpu-sample", type=int, default=512, help="lattice side of the CPU-baseline sample (0 = skip)")
-    ap.add_argument("--kappa", type=int, default=1, help="also time the kappa-map pipeline (1/0)")
-    ap.add_argument("--bispec", type=int, default=1, help="also time the 512^3 bispectrum (1/0)")
-    ap.add_argument("--legs", type=int, default=1, help="also time the shuffled-order and TSC legs (1/0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: streaming ceiling, the other legs, bispectrum, kappa "
+                         "pipeline, CPU baselines, paint-path statistics, per-site kernel times of the slab pipeline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step (k, power, modes) as DIR/<name>.npy")
+    ap.add_argument("--cpu-sample", type=int, default=None, help="lattice side of the CPU-baseline sample (0 = skip; default 512 with --full, else 0)")
+    ap.add_argument("--kappa", type=int, default=None, help="also time the kappa-map pipeline (1/0; default 1 with --full, else 0)")
+    ap.add_argument("--bispec", type=int, default=None, help="also time the 512^3 bispectrum (1/0; default 1 with --full, else 0)")
+    ap.add_argument("--legs", type=int, default=None, help="also time the shuffled-order and TSC legs (1/0; default 1 with --full, else 0)")
     ap.add_argument("--slab", type=int, default=0, help="run the slab-decomposed pipeline even on one GPU (rehearsal)")
     ap.add_argument("--cpu-paint-child", type=int, default=0, help="(internal) child mode of the CPU baseline's parallel paint")
     ap.add_argument("--cpu-workers", type=int, default=16, help="processes of the CPU baseline's parallel paint")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    # a plain run times the headline only; --full turns the secondary measurements on, an explicit value still wins
+    for name, full_default in (("cpu_sample", 512), ("kappa", 1), ("bispec", 1), ("legs", 1)):
+        if getattr(args, name) is None:
+            setattr(args, name, full_default if args.full else 0)
+    return args
+
+
+def dump_outputs(dirpath, outputs):
+    """--dump-outputs: the arrays the timed path returned from its last step, one .npy each, float32 / float64 (integer
+    counts widened to float64, exact below 2^53)."""
+    os.makedirs(dirpath, exist_ok=True)
+    for name, a in outputs.items():
+        a = np.asarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        np.save(os.path.join(dirpath, name + ".npy"), a)
 
 
 def _cpu_model():
@@ -557,7 +583,8 @@ def main():
         torch.cuda.synchronize()
 
     if not use_slab:
-        leg = power_leg(dev, n, npside, L, args.window, args.order, args.dtype, args.method, args.steps, args.warmup)
+        leg = power_leg(dev, n, npside, L, args.window, args.order, args.dtype, args.method, args.steps, args.warmup,
+                        path_stats=args.full)
     else:
         leg = slab_leg(dev, dist, n, npside, L, args, world, barrier, wd)
     ms_per_step = leg["ms_per_step"]
@@ -575,14 +602,16 @@ def main():
                                f"{args.window.upper()} paint on {n}^3 grid -> 3D R2C -> FFTPower 1d shells",
                    "ngrid": n, "nparticles": npart_total, "boxsize": L,
                    "order_note": "natural = lattice order, the spatially coherent best case for the scatter; the "
-                                 "shuffled (worst case), TSC and float64 figures are in `legs`",
+                                 "shuffled (worst case), TSC and float64 figures are in `legs` (--full)",
                    "outside_timed_step": "FFT twiddles, per-shell geometry sums (sum w|k|, mode counts: data independent, "
                                          "cached per (N, L) like an FFT plan), workspace allocation, the input probe that "
                                          "picks the paint path (once per particle array: config.paint_path.probe_ms)",
                    "parallelism": "single GPU" if not use_slab else f"axis-0 slabs x{world}, RCCL all-to-all transpose"},
         "roofline": roofline,
     }
-    if rank == 0 and not use_slab:
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, leg["outputs"])
+    if rank == 0 and not use_slab and (args.full or args.kappa):
         # every fraction above is of the data sheet's 8 TB/s; the same figures against what this GPU streams (measured here)
         ceil = stream_ceiling(dev)
         ceil["reading_the_fractions"] = ("frac_of_copy_rate = algorithmic GB/s / copy_GBps; a stage that moves fewer bytes than the "
@@ -728,9 +757,10 @@ def _traffic_from_profiles():
     return gb * 1e9, source
 
 
-def power_leg(dev, n, npside, L, window, order, dtype, method, steps, warmup, clustered=False):
+def power_leg(dev, n, npside, L, window, order, dtype, method, steps, warmup, clustered=False, path_stats=True):
     """One configuration of the 3D path on ONE GPU: paint -> 3D R2C -> shell binning, `steps` timed steps.
-    clustered: the lattice collapsing onto 256 attractors (tile occupancies ~100 x the mean) instead of the jittered lattice."""
+    clustered: the lattice collapsing onto 256 attractors (tile occupancies ~100 x the mean) instead of the jittered lattice.
+    path_stats: one more step after the timed ones for the paint's list statistics (`paint_path`)."""
     tdt = torch.float32 if dtype == "f32" else torch.float64
     esz = 4 if dtype == "f32" else 8
     npart_total = npside ** 3
@@ -828,19 +858,22 @@ def power_leg(dev, n, npside, L, window, order, dtype, method, steps, warmup, cl
                        "frac": round(total / (ms_per_step * 1e6) / HBM_PEAK_GBS, 4)},
         "stages": stages,
     }
-    # which path the timed paint took, how often it was attempted (always once: the path is chosen up front), what went
-    # through the overflow list: ONE more step, untimed, identical but for the list statistics it fetches
-    collect[0] = pstats
-    step()
-    collect[0] = None
-    torch.cuda.synchronize()
-    path = {"hint": hint, "path": pstats.get("path"), "attempts": pstats.get("attempts"), "overflow_list": pstats.get("overflow"),
-            "probe_ms": round(probe_ms, 3),
-            "probe": None if probe is None else {"groupable_runs": round(probe["groupable"], 3), "est_overflow": probe["overflow"],
-                                                 "est_max_tile_over_mean": round(probe["max_tile"] / max(1.0, probe["mean_tile"]), 1)}}
+    path = {"hint": hint}
+    if path_stats:
+        # which path the timed paint took, how often it was attempted (always once: the path is chosen up front), what went
+        # through the overflow list: ONE more step, untimed, identical but for the list statistics it fetches
+        collect[0] = pstats
+        step()
+        collect[0] = None
+        torch.cuda.synchronize()
+        path.update(path=pstats.get("path"), attempts=pstats.get("attempts"), overflow_list=pstats.get("overflow"))
+    path.update(probe_ms=round(probe_ms, 3),
+                probe=None if probe is None else {"groupable_runs": round(probe["groupable"], 3), "est_overflow": probe["overflow"],
+                                                  "est_max_tile_over_mean": round(probe["max_tile"] / max(1.0, probe["mean_tile"]), 1)})
     del pos, grid, spec
     torch.cuda.empty_cache()
-    return {"ms_per_step": ms_per_step, "roofline": roofline, "paint_path": path}
+    return {"ms_per_step": ms_per_step, "roofline": roofline, "paint_path": path,
+            "outputs": {"k": res["k"], "power": res["power"], "modes": res["modes"]}}
 
 
 def slab_leg(dev, dist, n, npside, L, args, world, barrier, wd):
@@ -863,62 +896,67 @@ def slab_leg(dev, dist, n, npside, L, args, world, barrier, wd):
     barrier()
     wd.beat("timed steps")
     # the timed steps run WITHOUT the per-launch-site event pairs: a staged step makes ~45 small launches, and the events
-    # around them cost 0.2-0.4 ms per step (measured, scripts/perf_slab_staged.py); the per-site kernel times of the line
-    # come from `prof_steps` extra steps right after the timed region
+    # around them cost 0.2-0.4 ms per step (measured, scripts/perf_slab_staged.py); with --full the per-site kernel times of
+    # the line come from `prof_steps` extra steps right after the timed region
     t0 = time.perf_counter()
     for _ in range(args.steps):
         sums = pipe.step()
     barrier()
     elapsed = time.perf_counter() - t0
-    wd.beat("timed steps done; profiled steps")
-    prof_steps = max(2, min(args.steps, 5))
-    pipe.stage_ms(args.steps)            # (reset the host-stage clock)
-    dev.profile_enable(True)
-    for _ in range(prof_steps):
-        pipe.step()
-    barrier()
-    prof = dev.profile_report()
-    dev.profile_enable(False)
-    prof = {k: (v[0], v[1] * args.steps / prof_steps) for k, v in prof.items()}      # scaled to the timed step count
-    wd.beat("profiled steps done")
-    # diagnostics of the N > 1 line: every rank's own wall time and per-site kernel times, and what a step puts on
-    # the links (so that the first run on real xGMI says where the time went)
-    mine = {"rank": dist.get_rank(), "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "kernels_ms": {k: round(v[1] / args.steps, 4) for k, v in prof.items()},
-            "stage_ms": {k: round(v, 4) for k, v in pipe.stage_ms(prof_steps).items()}}
+    wd.beat("timed steps done")
+    res = dev.finish_power(*sums)            # the last timed step's spectrum (the profiled steps below reuse its buffers)
+    assert np.isfinite(res["power"]).all() and res["power"][-1] > 0
+    outputs = {"k": res["k"], "power": res["power"], "modes": res["modes"]}
+    mine = {"rank": dist.get_rank(), "ms_per_step": round(elapsed / args.steps * 1e3, 4)}
+    prof = None
+    if args.full:
+        wd.beat("profiled steps")
+        prof_steps = max(2, min(args.steps, 5))
+        pipe.stage_ms(args.steps)            # (reset the host-stage clock)
+        dev.profile_enable(True)
+        for _ in range(prof_steps):
+            pipe.step()
+        barrier()
+        prof = dev.profile_report()
+        dev.profile_enable(False)
+        prof = {k: (v[0], v[1] * args.steps / prof_steps) for k, v in prof.items()}      # scaled to the timed step count
+        wd.beat("profiled steps done")
+        # diagnostics of the N > 1 line: every rank's own wall time and per-site kernel times, and what a step puts on
+        # the links (so that the first run on real xGMI says where the time went)
+        mine["kernels_ms"] = {k: round(v[1] / args.steps, 4) for k, v in prof.items()}
+        mine["stage_ms"] = {k: round(v, 4) for k, v in pipe.stage_ms(prof_steps).items()}
     per_rank = [None] * world
     dist.all_gather_object(per_rank, mine)
     tmax = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
     dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     elapsed = float(tmax.item())
     ms_per_step = elapsed / args.steps * 1e3
-    res = dev.finish_power(*sums)
-    assert np.isfinite(res["power"]).all() and res["power"][-1] > 0
-    overlapped = ("paint_tiled.fill", "paint_tiled.deposit") if "paint_tiled.pipeline" in prof else ()
-    stages, stage_sites, stage_bytes = _stage_table(prof, args.steps, npside ** 3 / world, n ** 3 / world, esz, fused_bin=False,
-                                                    concurrent=overlapped)
-    dom = max(stages, key=lambda k: stages[k]["ms"])
-    total = sum(stage_bytes.values())
-    roofline = {
-        "bound": "hbm", "kernel": f"{dom} stage ({'+'.join(stage_sites[dom])}), rank 0 of {world}",
-        "achieved": stages[dom]["GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-        "frac": stages[dom]["frac"], "traffic": None,
-        "end_to_end": {"alg_GB": round(total * world / 1e9, 3), "GBps": round(total * world / (ms_per_step * 1e6), 1),
-                       "frac": round(total / (ms_per_step * 1e6) / HBM_PEAK_GBS, 4)},
-        "stages": stages, "ranks": world, "backend": dist.get_backend(),
-    }
-    return {"ms_per_step": ms_per_step, "roofline": roofline,
+    roofline = None                          # (a plain run: no per-site kernel times, no stage table)
+    if prof is not None:
+        overlapped = ("paint_tiled.fill", "paint_tiled.deposit") if "paint_tiled.pipeline" in prof else ()
+        stages, stage_sites, stage_bytes = _stage_table(prof, args.steps, npside ** 3 / world, n ** 3 / world, esz, fused_bin=False,
+                                                        concurrent=overlapped)
+        dom = max(stages, key=lambda k: stages[k]["ms"])
+        total = sum(stage_bytes.values())
+        roofline = {
+            "bound": "hbm", "kernel": f"{dom} stage ({'+'.join(stage_sites[dom])}), rank 0 of {world}",
+            "achieved": stages[dom]["GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": stages[dom]["frac"], "traffic": None,
+            "end_to_end": {"alg_GB": round(total * world / 1e9, 3), "GBps": round(total * world / (ms_per_step * 1e6), 1),
+                           "frac": round(total / (ms_per_step * 1e6) / HBM_PEAK_GBS, 4)},
+            "stages": stages, "ranks": world, "backend": dist.get_backend(),
+        }
+    return {"ms_per_step": ms_per_step, "roofline": roofline, "outputs": outputs,
             "diag": {"world_size": dist.get_world_size(), "backend": dist.get_backend(),
                      "wire_bytes_per_step_per_rank": pipe.wire_bytes(), "pipeline": pipe.pipeline,
-                     "kernel_times_from": f"{prof_steps} steps run right after the timed region with the per-site events on "
-                                          "(the timed steps run without them)",
+                     "kernel_times_from": (f"{prof_steps} steps run right after the timed region with the per-site events on "
+                                           "(the timed steps run without them)" if prof is not None else None),
                      "schedule": [list(e) for e in pipe.schedule] if pipe.schedule else None, "chunks": pipe.chunks,
                      "spectrum_row_pitch": pipe.nzp, "nx_alloc": pipe.nx_alloc,
                      "transpose_layout": ("rows" if pipe.disc is None else
                                           {"kind": "disc (only what FFTPower keeps; k_y row blocks dealt to the ranks by disc area)",
                                            "plane_elems_per_part": pipe.disc["S"], "full_pitched_plane_elems": pipe.nloc * pipe.nzp}),
                      "per_rank": per_rank}}
-
 
 if __name__ == "__main__":
     main()

@@ -1,5 +1,5 @@
 """HBM traffic of ONE bispectrum evaluation (config E) from two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of
-`bench.py --cpu-sample 0 --kappa 0 --legs 0 --steps 1 --warmup 0`, whose bispectrum leg calls the estimator twice (the
+`bench.py --full --cpu-sample 0 --kappa 0 --legs 0 --steps 1 --warmup 0`, whose bispectrum leg calls the estimator twice (the
 first call also computes the cached triangle counts).  Corrected bytes = (2 FETCH_SIZE + WRITE_SIZE) KiB (MI355X_MICROARCH.md).
 usage: pmc_bispec_json.py <fetch_dir> <write_dir> <out.json>"""
 import csv, glob, hashlib, json, os, sys, collections

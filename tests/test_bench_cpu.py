@@ -45,3 +45,27 @@ def test_auto_paint_method_thresholds():
     assert m(40 * per_tile, n, n, "cic", accumulate=True) == "direct" and m(64 * per_tile, n, n, "cic", accumulate=True) == "tiled"
     assert m(10 ** 7, 100, 100, "cic") == "direct"                                                       # nmesh not a multiple of 32
     assert m(1000, n, n, "cic") == "direct"
+
+
+def test_plain_run_times_the_headline_only(monkeypatch):
+    """A plain run turns every secondary measurement off; --full turns them on as before; an explicit switch still wins."""
+    import bench
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.full, a.cpu_sample, a.kappa, a.bispec, a.legs, a.steps, a.warmup, a.dump_outputs) == (False, 0, 0, 0, 0, 7, 2, None)
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--kappa", "0"])
+    a = bench.parse()
+    assert (a.full, a.cpu_sample, a.kappa, a.bispec, a.legs) == (True, 512, 0, 1, 1)
+    monkeypatch.setattr("sys.argv", ["bench.py", "--cpu-sample", "1024"])
+    assert bench.parse().cpu_sample == 1024
+
+
+def test_dump_outputs_writes_float_arrays(tmp_path):
+    import bench
+    out = tmp_path / "dump"
+    bench.dump_outputs(str(out), {"k": np.linspace(0.1, 1.0, 5), "power": np.ones(5, np.float32),
+                                  "modes": np.arange(5, dtype=np.int64)})
+    got = {p.stem: np.load(p) for p in out.glob("*.npy")}
+    assert sorted(got) == ["k", "modes", "power"]
+    assert got["k"].dtype == np.float64 and got["power"].dtype == np.float32 and got["modes"].dtype == np.float64
+    np.testing.assert_array_equal(got["modes"], np.arange(5))
