@@ -147,6 +147,10 @@ SIGNATURES = {
     "ast_gaussian_filter_order": (_i, [_vp, _vp, _vp, _sz, _i, _d, _i, _i, _i, _vp]),
     "ast_convolve2d": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "ast_aperture_photometry": (_i, [_vp, _vp, _vp, _i, _d, _vp]),
+    "ast_pairwise_workspace_bytes": (_sz, [_sz, _i]),
+    "ast_pairwise_max_bins": (_i, []),
+    "ast_pairwise_tv_prepare": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _sz, _vp, _sz, _vp]),
+    "ast_pairwise_tv": (_i, [_vp, _sz, _sz, _i, _d, _i, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

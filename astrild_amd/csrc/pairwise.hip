@@ -1,0 +1,459 @@
+// Mean pairwise velocity from transverse velocities (Yasini et al. 2018), the estimator of
+// particles/hutils/mean_pairwise_velocity.py: per-object prep, a uniform cell grid (counting sort by cell) as the
+// pair finder, a tiled pair kernel with per-workgroup LDS histograms, and a fixed-order sum of the workgroup rows.
+// All pair arithmetic is fp64 (the library is built with -ffp-contract=off: op-by-op IEEE, like numpy).
+#include "ast_common.h"
+#include <cmath>
+
+namespace {
+
+constexpr int PV_BLOCK = 256;               // i objects per tile = j objects per LDS stage
+constexpr int PV_WAVES = PV_BLOCK / 64;
+constexpr int PV_GRID = 1024;               // persistent pair-kernel workgroups (256 CUs x 4)
+constexpr int PV_NEIGH = 14;                // the cell itself + 13 half-shell neighbours
+constexpr size_t PV_MAX_CELLS = size_t(1) << 20;
+constexpr int PV_MAX_BINS = 480;            // 4 wave histograms x 24 B x bins + the j stage fit 64 KiB of LDS
+
+struct PvObj { double r[3], u[3], t[3]; };
+
+struct PvParams {
+    unsigned long long kmin[3], kmax[3];    // bounding box as order-preserving keys (atomicMin / atomicMax)
+    double lo[3], inv_cs[3];
+    int dims[3];
+    unsigned ncells, ntiles;
+};
+
+inline size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
+inline size_t cells_cap(size_t n) { return n < 1 ? 1 : (n < PV_MAX_CELLS ? n : PV_MAX_CELLS); }
+
+struct PvLayout {
+    size_t params, cnt, cell_start, tile_start, cursor, cell_of, obj, sorted, part, total;
+    PvLayout(size_t n, int binnr) {
+        const size_t cap = cells_cap(n);
+        size_t o = 0;
+        params = o;     o += align256(sizeof(PvParams));
+        cnt = o;        o += align256(cap * 4);
+        cell_start = o; o += align256((cap + 1) * 4);
+        tile_start = o; o += align256((cap + 1) * 4);
+        cursor = o;     o += align256(cap * 4);
+        cell_of = o;    o += align256(n * 4);
+        obj = o;        o += align256(n * sizeof(PvObj));
+        sorted = o;     o += align256(n * sizeof(PvObj));
+        part = o;       o += align256((size_t)PV_GRID * (size_t)binnr * 24);
+        total = o;
+    }
+};
+
+__device__ inline unsigned long long d2key(double d) {
+    unsigned long long u = (unsigned long long)__double_as_longlong(d);
+    return (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
+}
+__device__ inline double key2d(unsigned long long k) {
+    unsigned long long u = (k & 0x8000000000000000ull) ? (k & 0x7fffffffffffffffull) : ~k;
+    return __longlong_as_double((long long)u);
+}
+__device__ inline double wave_min(double v) {
+    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ inline double wave_max(double v) {
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+// One thread per object: r (widened to fp64), u = r / |r|, and the cartesian transverse velocity
+// t = J(th = theta2, ph = theta1)^T (0, v1, v2) of get_sph_to_cart_jacobian (or v itself when 3 components are given).
+// angle_mode 0: theta1 = arctan(x / z), theta2 = arctan(y / z), both + 10 deg; 1: given in radians; 2: given in degrees.
+// The bounding box of r goes to prm->kmin / kmax, one atomic per workgroup and axis.
+template <typename TP, typename TV>
+__global__ void __launch_bounds__(256)
+pv_prep_kernel(const TP* __restrict__ pos, const TV* __restrict__ vel, int vel_ncomp, const double* __restrict__ th1,
+               const double* __restrict__ th2, int angle_mode, size_t n, PvObj* __restrict__ obj, PvParams* prm) {
+    __shared__ double wlo[3][4], whi[3][4];
+    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        PvObj o;
+        const double x = (double)pos[3 * i], y = (double)pos[3 * i + 1], z = (double)pos[3 * i + 2];
+        o.r[0] = x; o.r[1] = y; o.r[2] = z;
+        const double nr = sqrt((x * x + y * y) + z * z);
+        o.u[0] = x / nr; o.u[1] = y / nr; o.u[2] = z / nr;
+        if (vel_ncomp == 3) {
+            o.t[0] = (double)vel[3 * i]; o.t[1] = (double)vel[3 * i + 1]; o.t[2] = (double)vel[3 * i + 2];
+        } else {
+            double ph, th;
+            if (angle_mode == 0) {
+                constexpr double shift = 10 * M_PI / 180;
+                ph = atan(x / z) + shift;
+                th = atan(y / z) + shift;
+            } else if (angle_mode == 2) {
+                ph = th1[i] * (M_PI / 180.0);
+                th = th2[i] * (M_PI / 180.0);
+            } else {
+                ph = th1[i];
+                th = th2[i];
+            }
+            const double v1 = (double)vel[2 * i], v2 = (double)vel[2 * i + 1];
+            const double st = sin(th), ct = cos(th), sp = sin(ph), cp = cos(ph);
+            // einsum('ij...,i...->j...', J, (0, v1, v2)): rows 2 and 3 of J weighted by v1, v2
+            o.t[0] = (0.0 + v1 * (ct * cp)) + v2 * (-sp);
+            o.t[1] = (0.0 + v1 * (ct * sp)) + v2 * cp;
+            o.t[2] = (0.0 + v1 * (-st)) + v2 * (0.0 * ct);
+        }
+        obj[i] = o;
+        for (int a = 0; a < 3; ++a) { lo[a] = fmin(lo[a], o.r[a]); hi[a] = fmax(hi[a], o.r[a]); }
+    }
+    const int w = threadIdx.x / 64, l = threadIdx.x % 64;
+    for (int a = 0; a < 3; ++a) {
+        const double mn = wave_min(lo[a]), mx = wave_max(hi[a]);
+        if (l == 0) { wlo[a][w] = mn; whi[a][w] = mx; }
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const int a = threadIdx.x;
+        double mn = wlo[a][0], mx = whi[a][0];
+        for (int k = 1; k < 4; ++k) { mn = fmin(mn, wlo[a][k]); mx = fmax(mx, whi[a][k]); }
+        if (mn <= mx) {
+            atomicMin(&prm->kmin[a], d2key(mn));
+            atomicMax(&prm->kmax[a], d2key(mx));
+        }
+    }
+}
+
+// One thread: the grid.  Cells are at least `target` = rmax (1 + 1e-6) wide per axis (plus a margin for the rounding
+// of coordinates far from the origin), so a pair within reach lies in the same or an adjacent cell; at most `cap`
+// cells in all (wider cells past that).  single != 0: one cell (ASTRILD_PV_CELLS=0).
+__global__ void pv_plan_kernel(PvParams* prm, double rmax, unsigned cap, int single) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    double lo[3], ext[3], amax = 0.0;
+    for (int a = 0; a < 3; ++a) {
+        lo[a] = key2d(prm->kmin[a]);
+        const double hi = key2d(prm->kmax[a]);
+        ext[a] = hi - lo[a];
+        amax = fmax(amax, fmax(fabs(lo[a]), fabs(hi)));
+    }
+    int dims[3] = {1, 1, 1};
+    if (!single) {
+        double s = rmax * (1.0 + 1e-6) + amax * 1e-12;
+        for (;;) {
+            double prod = 1.0;
+            for (int a = 0; a < 3; ++a) {
+                double m = floor(ext[a] / s);
+                if (!(m >= 1.0)) m = 1.0;
+                if (m > (double)PV_MAX_CELLS) m = (double)PV_MAX_CELLS;
+                dims[a] = (int)m;
+                prod *= m;
+            }
+            if (prod <= (double)cap) break;
+            s *= 1.25;
+        }
+    }
+    for (int a = 0; a < 3; ++a) {
+        prm->lo[a] = lo[a];
+        prm->dims[a] = dims[a];
+        prm->inv_cs[a] = dims[a] > 1 ? (double)dims[a] / ext[a] : 0.0;
+    }
+    prm->ncells = (unsigned)dims[0] * (unsigned)dims[1] * (unsigned)dims[2];
+}
+
+__device__ inline unsigned pv_cell(const PvObj& o, const PvParams& p) {
+    int c[3];
+    for (int a = 0; a < 3; ++a) {
+        double v = (o.r[a] - p.lo[a]) * p.inv_cs[a];
+        const double top = (double)(p.dims[a] - 1);
+        if (!(v >= 0.0)) v = 0.0;
+        if (v > top) v = top;
+        c[a] = (int)v;
+    }
+    return ((unsigned)c[2] * (unsigned)p.dims[1] + (unsigned)c[1]) * (unsigned)p.dims[0] + (unsigned)c[0];
+}
+
+__global__ void __launch_bounds__(256)
+pv_count_kernel(const PvObj* __restrict__ obj, size_t n, const PvParams* prm, unsigned* __restrict__ cell_of,
+                unsigned* __restrict__ cnt) {
+    const PvParams p = *prm;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const unsigned c = pv_cell(obj[i], p);
+        cell_of[i] = c;
+        atomicAdd(&cnt[c], 1u);
+    }
+}
+
+// One workgroup of 1024: exclusive scans of the cell counts (-> cell_start, cursor) and of the tiles per cell,
+// ceil(count / PV_BLOCK) (-> tile_start); ntiles = the total.  Each thread scans a contiguous chunk.
+__global__ void __launch_bounds__(1024)
+pv_scan_kernel(const unsigned* __restrict__ cnt, PvParams* prm, unsigned* __restrict__ cell_start,
+               unsigned* __restrict__ tile_start, unsigned* __restrict__ cursor) {
+    __shared__ unsigned s_obj[1024], s_til[1024];
+    const unsigned nc = prm->ncells;
+    const unsigned chunk = (nc + 1023) / 1024;
+    const unsigned c0 = threadIdx.x * chunk, c1 = min(nc, c0 + chunk);
+    unsigned so = 0, st = 0;
+    for (unsigned c = c0; c < c1; ++c) { so += cnt[c]; st += (cnt[c] + PV_BLOCK - 1) / PV_BLOCK; }
+    s_obj[threadIdx.x] = so;
+    s_til[threadIdx.x] = st;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned ao = 0, at = 0;
+        for (int k = 0; k < 1024; ++k) {
+            const unsigned vo = s_obj[k], vt = s_til[k];
+            s_obj[k] = ao; s_til[k] = at;
+            ao += vo; at += vt;
+        }
+        cell_start[nc] = ao;
+        tile_start[nc] = at;
+        prm->ntiles = at;
+    }
+    __syncthreads();
+    so = s_obj[threadIdx.x];
+    st = s_til[threadIdx.x];
+    for (unsigned c = c0; c < c1; ++c) {
+        cell_start[c] = so;
+        cursor[c] = so;
+        tile_start[c] = st;
+        so += cnt[c];
+        st += (cnt[c] + PV_BLOCK - 1) / PV_BLOCK;
+    }
+}
+
+__global__ void __launch_bounds__(256)
+pv_scatter_kernel(const PvObj* __restrict__ obj, size_t n, const unsigned* __restrict__ cell_of,
+                  unsigned* __restrict__ cursor, PvObj* __restrict__ sorted) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const unsigned slot = atomicAdd(&cursor[cell_of[i]], 1u);
+        sorted[slot] = obj[i];
+    }
+}
+
+__constant__ int pv_offsets[PV_NEIGH][3] = {
+    {0, 0, 0},
+    {1, 0, 0},
+    {-1, 1, 0}, {0, 1, 0}, {1, 1, 0},
+    {-1, -1, 1}, {0, -1, 1}, {1, -1, 1},
+    {-1, 0, 1}, {0, 0, 1}, {1, 0, 1},
+    {-1, 1, 1}, {0, 1, 1}, {1, 1, 1},
+};
+
+// Work item = (tile of PV_BLOCK objects of cell a, neighbour k): each thread holds one i of the tile, the j objects of
+// cell a + offset[k] pass through LDS PV_BLOCK at a time (k = 0: the cell itself, j > i only).  A persistent grid walks
+// the items with a fixed stride; each wave adds into its own LDS histogram (nom, denom, pairs), and at the end the
+// workgroup's row (waves summed in order) is stored to part - no global atomics.
+__global__ void __launch_bounds__(PV_BLOCK)
+pv_pair_kernel(const PvObj* __restrict__ sorted, const unsigned* __restrict__ cell_start,
+               const unsigned* __restrict__ tile_start, const PvParams* prm, int binnr, double binwidth,
+               double reach2, double* __restrict__ part) {
+    extern __shared__ double lds[];
+    double* jr = lds;                                   // [9][PV_BLOCK]: r, u, t of the staged j objects
+    double* hn = lds + 9 * PV_BLOCK;                    // [PV_WAVES][binnr]
+    double* hd = hn + PV_WAVES * binnr;
+    unsigned long long* hc = (unsigned long long*)(hd + PV_WAVES * binnr);
+    const int tid = threadIdx.x, w = tid / 64;
+    for (int k = tid; k < PV_WAVES * binnr; k += PV_BLOCK) { hn[k] = 0.0; hd[k] = 0.0; hc[k] = 0ull; }
+    double* whn = hn + w * binnr;
+    double* whd = hd + w * binnr;
+    unsigned long long* whc = hc + w * binnr;
+
+    const int dx = prm->dims[0], dy = prm->dims[1], dz = prm->dims[2];
+    const unsigned ncells = prm->ncells;
+    const unsigned long long nitems = (unsigned long long)prm->ntiles * PV_NEIGH;
+    for (unsigned long long item = blockIdx.x; item < nitems; item += gridDim.x) {
+        const unsigned tile = (unsigned)(item / PV_NEIGH);
+        const int k = (int)(item % PV_NEIGH);
+        unsigned lo = 0, hi = ncells;                   // tile_start[lo] <= tile < tile_start[hi]
+        while (hi - lo > 1) {
+            const unsigned mid = (lo + hi) / 2;
+            if (tile_start[mid] <= tile) lo = mid; else hi = mid;
+        }
+        const unsigned a = lo;
+        const int ax = (int)(a % (unsigned)dx), ay = (int)((a / (unsigned)dx) % (unsigned)dy), az = (int)(a / ((unsigned)dx * (unsigned)dy));
+        const int bx = ax + pv_offsets[k][0], by = ay + pv_offsets[k][1], bz = az + pv_offsets[k][2];
+        if (bx < 0 || bx >= dx || by < 0 || by >= dy || bz < 0 || bz >= dz) continue;
+        const unsigned b = ((unsigned)bz * (unsigned)dy + (unsigned)by) * (unsigned)dx + (unsigned)bx;
+        const unsigned i0 = cell_start[a] + (tile - tile_start[a]) * PV_BLOCK;
+        const unsigned i1 = min(i0 + PV_BLOCK, cell_start[a + 1]);
+        const unsigned j0 = k == 0 ? i0 + 1 : cell_start[b];
+        const unsigned j1 = cell_start[b + 1];
+        if (j0 >= j1) continue;
+
+        const unsigned i = i0 + tid;
+        const bool valid = i < i1;
+        PvObj oi;
+        if (valid) oi = sorted[i];
+        for (unsigned jc = j0; jc < j1; jc += PV_BLOCK) {
+            __syncthreads();
+            if (jc + tid < j1) {
+                const PvObj oj = sorted[jc + tid];
+                for (int c = 0; c < 3; ++c) {
+                    jr[c * PV_BLOCK + tid] = oj.r[c];
+                    jr[(3 + c) * PV_BLOCK + tid] = oj.u[c];
+                    jr[(6 + c) * PV_BLOCK + tid] = oj.t[c];
+                }
+            }
+            __syncthreads();
+            if (!valid) continue;
+            const int m = (int)min((unsigned)PV_BLOCK, j1 - jc);
+            const int q0 = (k == 0 && i + 1 > jc) ? (int)min((unsigned)m, i + 1 - jc) : 0;
+            for (int q = q0; q < m; ++q) {
+                const double ddx = oi.r[0] - jr[q], ddy = oi.r[1] - jr[PV_BLOCK + q], ddz = oi.r[2] - jr[2 * PV_BLOCK + q];
+                const double d2 = (ddx * ddx + ddy * ddy) + ddz * ddz;
+                if (!(d2 <= reach2)) continue;
+                const double d = sqrt(d2);
+                const int bin = (int)(d / binwidth);
+                if (bin >= binnr) continue;
+                const double px = ddx / d, py = ddy / d, pz = ddz / d;
+                const double ujx = jr[3 * PV_BLOCK + q], ujy = jr[4 * PV_BLOCK + q], ujz = jr[5 * PV_BLOCK + q];
+                const double pi_ = (px * oi.u[0] + py * oi.u[1]) + pz * oi.u[2];
+                const double pj_ = (px * ujx + py * ujy) + pz * ujz;
+                const double qx = 0.5 * ((2.0 * px - oi.u[0] * pi_) - ujx * pj_);
+                const double qy = 0.5 * ((2.0 * py - oi.u[1] * pi_) - ujy * pj_);
+                const double qz = 0.5 * ((2.0 * pz - oi.u[2] * pi_) - ujz * pj_);
+                const double tx = oi.t[0] - jr[6 * PV_BLOCK + q], ty = oi.t[1] - jr[7 * PV_BLOCK + q],
+                             tz = oi.t[2] - jr[8 * PV_BLOCK + q];
+                atomicAdd(&whn[bin], (tx * qx + ty * qy) + tz * qz);
+                atomicAdd(&whd[bin], (qx * qx + qy * qy) + qz * qz);
+                atomicAdd(&whc[bin], 1ull);
+            }
+        }
+    }
+    __syncthreads();
+    double* pn = part;
+    double* pd = part + (size_t)PV_GRID * binnr;
+    unsigned long long* pc = (unsigned long long*)(part + 2 * (size_t)PV_GRID * binnr);
+    for (int bin = tid; bin < binnr; bin += PV_BLOCK) {
+        double sn = hn[bin], sd = hd[bin];
+        unsigned long long sc = hc[bin];
+        for (int v = 1; v < PV_WAVES; ++v) { sn += hn[v * binnr + bin]; sd += hd[v * binnr + bin]; sc += hc[v * binnr + bin]; }
+        const size_t o = (size_t)blockIdx.x * binnr + bin;
+        pn[o] = sn;
+        pd[o] = sd;
+        pc[o] = sc;
+    }
+}
+
+// out[bin] = sum of the PV_GRID workgroup rows, in row order.
+__global__ void __launch_bounds__(256)
+pv_reduce_kernel(const double* __restrict__ part, int binnr, double* __restrict__ nom, double* __restrict__ denom,
+                 unsigned long long* __restrict__ counts) {
+    const int bin = blockIdx.x * blockDim.x + threadIdx.x;
+    if (bin >= binnr) return;
+    const double* pn = part;
+    const double* pd = part + (size_t)PV_GRID * binnr;
+    const unsigned long long* pc = (const unsigned long long*)(part + 2 * (size_t)PV_GRID * binnr);
+    double sn = 0.0, sd = 0.0;
+    unsigned long long sc = 0;
+    for (int g = 0; g < PV_GRID; ++g) {
+        const size_t o = (size_t)g * binnr + bin;
+        sn += pn[o];
+        sd += pd[o];
+        sc += pc[o];
+    }
+    nom[bin] = sn;
+    denom[bin] = sd;
+    counts[bin] = sc;
+}
+
+template <typename TP, typename TV>
+void launch_prep(const void* pos, const void* vel, int vel_ncomp, const double* th1, const double* th2, int angle_mode,
+                 size_t n, PvObj* obj, PvParams* prm, hipStream_t s) {
+    pv_prep_kernel<TP, TV><<<ast::stream_grid(n, 256), 256, 0, s>>>((const TP*)pos, (const TV*)vel, vel_ncomp, th1, th2,
+                                                                     angle_mode, n, obj, prm);
+}
+
+}  // namespace
+
+extern "C" size_t ast_pairwise_workspace_bytes(size_t n, int binnr) {
+    if (binnr < 1 || binnr > PV_MAX_BINS) return 0;
+    return PvLayout(n, binnr).total;
+}
+
+extern "C" int ast_pairwise_max_bins(void) { return PV_MAX_BINS; }
+
+extern "C" int ast_pairwise_tv_prepare(const void* pos_d, int pos_dtype, const void* vel_d, int vel_dtype, int vel_ncomp,
+                                       const double* theta1_d, const double* theta2_d, int angle_mode, size_t n,
+                                       void* work_d, size_t work_bytes, void* stream) {
+    AST_CHECK_ARG(pos_dtype == AST_F32 || pos_dtype == AST_F64);
+    AST_CHECK_ARG(vel_dtype == AST_F32 || vel_dtype == AST_F64);
+    AST_CHECK_ARG(vel_ncomp == 2 || vel_ncomp == 3);
+    AST_CHECK_ARG(angle_mode >= 0 && angle_mode <= 2);
+    AST_CHECK_ARG(angle_mode == 0 || vel_ncomp == 3 || n == 0 || (theta1_d && theta2_d));
+    AST_CHECK_ARG(n < (size_t(1) << 31));
+    AST_CHECK_ARG(n == 0 || (pos_d && vel_d));
+    AST_CHECK_ARG(work_d && work_bytes >= PvLayout(n, 1).obj + align256(n * sizeof(PvObj)));
+    hipStream_t s = ast::as_stream(stream);
+    const PvLayout L(n, 1);
+    char* ws = (char*)work_d;
+    PvParams* prm = (PvParams*)(ws + L.params);
+    AST_CHECK_HIP(hipMemsetAsync(prm->kmin, 0xff, sizeof(prm->kmin), s));
+    AST_CHECK_HIP(hipMemsetAsync(prm->kmax, 0x00, sizeof(prm->kmax), s));
+    if (n == 0) return AST_OK;
+    AST_PROF("pairwise_prep", s);
+    PvObj* obj = (PvObj*)(ws + L.obj);
+    if (pos_dtype == AST_F32 && vel_dtype == AST_F32)
+        launch_prep<float, float>(pos_d, vel_d, vel_ncomp, theta1_d, theta2_d, angle_mode, n, obj, prm, s);
+    else if (pos_dtype == AST_F32)
+        launch_prep<float, double>(pos_d, vel_d, vel_ncomp, theta1_d, theta2_d, angle_mode, n, obj, prm, s);
+    else if (vel_dtype == AST_F32)
+        launch_prep<double, float>(pos_d, vel_d, vel_ncomp, theta1_d, theta2_d, angle_mode, n, obj, prm, s);
+    else
+        launch_prep<double, double>(pos_d, vel_d, vel_ncomp, theta1_d, theta2_d, angle_mode, n, obj, prm, s);
+    AST_CHECK_LAUNCH();
+    return AST_OK;
+}
+
+extern "C" int ast_pairwise_tv(void* work_d, size_t work_bytes, size_t n, int binnr, double binwidth, int single_cell,
+                               double* nom_d, double* denom_d, unsigned long long* counts_d, void* stream) {
+    AST_CHECK_ARG(binnr >= 1 && binnr <= PV_MAX_BINS);
+    AST_CHECK_ARG(binwidth > 0.0 && std::isfinite(binwidth));
+    AST_CHECK_ARG(n < (size_t(1) << 31));
+    AST_CHECK_ARG(nom_d && denom_d && counts_d);
+    AST_CHECK_ARG(work_d && work_bytes >= ast_pairwise_workspace_bytes(n, binnr));
+    hipStream_t s = ast::as_stream(stream);
+    if (n < 2) {
+        AST_CHECK_HIP(hipMemsetAsync(nom_d, 0, binnr * sizeof(double), s));
+        AST_CHECK_HIP(hipMemsetAsync(denom_d, 0, binnr * sizeof(double), s));
+        AST_CHECK_HIP(hipMemsetAsync(counts_d, 0, binnr * sizeof(unsigned long long), s));
+        return AST_OK;
+    }
+    const PvLayout L(n, binnr);
+    char* ws = (char*)work_d;
+    PvParams* prm = (PvParams*)(ws + L.params);
+    unsigned* cnt = (unsigned*)(ws + L.cnt);
+    unsigned* cell_start = (unsigned*)(ws + L.cell_start);
+    unsigned* tile_start = (unsigned*)(ws + L.tile_start);
+    unsigned* cursor = (unsigned*)(ws + L.cursor);
+    unsigned* cell_of = (unsigned*)(ws + L.cell_of);
+    const PvObj* obj = (const PvObj*)(ws + L.obj);
+    PvObj* sorted = (PvObj*)(ws + L.sorted);
+    double* part = (double*)(ws + L.part);
+    const size_t cap = cells_cap(n);
+    const double rmax = (double)binnr * binwidth;
+    {
+        AST_PROF("pairwise_grid", s);
+        pv_plan_kernel<<<1, 64, 0, s>>>(prm, rmax, (unsigned)cap, single_cell);
+        AST_CHECK_LAUNCH();
+        AST_CHECK_HIP(hipMemsetAsync(cnt, 0, cap * 4, s));
+        pv_count_kernel<<<ast::stream_grid(n, 256), 256, 0, s>>>(obj, n, prm, cell_of, cnt);
+        AST_CHECK_LAUNCH();
+        pv_scan_kernel<<<1, 1024, 0, s>>>(cnt, prm, cell_start, tile_start, cursor);
+        AST_CHECK_LAUNCH();
+        pv_scatter_kernel<<<ast::stream_grid(n, 256), 256, 0, s>>>(obj, n, cell_of, cursor, sorted);
+        AST_CHECK_LAUNCH();
+    }
+    // Pre-test on d^2 with a relative margin far above the rounding of d and d / binwidth: every pair whose
+    // int(d / binwidth) < binnr passes it; the bin decision itself is the fp64 int(d / binwidth) < binnr.
+    const double reach2 = rmax * rmax * (1.0 + 1e-12);
+    const size_t lds = (size_t)9 * PV_BLOCK * sizeof(double) + (size_t)PV_WAVES * binnr * 24;
+    {
+        AST_PROF("pairwise_pairs", s);
+        pv_pair_kernel<<<PV_GRID, PV_BLOCK, lds, s>>>(sorted, cell_start, tile_start, prm, binnr, binwidth, reach2, part);
+        AST_CHECK_LAUNCH();
+    }
+    {
+        AST_PROF("pairwise_reduce", s);
+        pv_reduce_kernel<<<(binnr + 255) / 256, 256, 0, s>>>(part, binnr, nom_d, denom_d, counts_d);
+        AST_CHECK_LAUNCH();
+    }
+    return AST_OK;
+}

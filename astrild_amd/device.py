@@ -1123,3 +1123,46 @@ def bispectrum(field, boxsize, edges, triangles):
     with np.errstate(invalid="ignore", divide="ignore"):
         b = float(boxsize) ** 6 * num / (ntri * float(n) ** 3)
     return {"B": b, "ntri": ntri, "k": kmid, "ntri_residual": _tri_cache[key + ("residual",)]}
+
+
+# ------------------------------------------------------------------ mean pairwise velocity
+def pairwise_tv(pos, vel_cart_or_ang, binnr, binwidth, theta1=None, theta2=None):
+    """Pair sums of the transverse-velocity pairwise estimator (mean_pairwise_velocity.py, Yasini et al. 2018) on the
+    GPU: ``(nom, denom, counts)``, device tensors of ``binnr`` float64 / float64 / int64.  A pair lands in bin
+    ``int(|r_i - r_j| / binwidth)`` when that is below ``binnr``.  ``pos`` (N, 3); ``vel_cart_or_ang`` (N, 2): RA / DEC
+    transverse velocities, turned cartesian with the angles (``theta1`` / ``theta2``: radians, or degrees when
+    ``max(theta1) > 2 pi``; None: arctan(x / z), arctan(y / z) + 10 deg, as the reference), or (N, 3): cartesian
+    already.  numpy arrays or device tensors, float32 or float64 (widened to float64 on load).
+    ASTRILD_PV_CELLS=0 forces one cell (all pairs) instead of the cell grid."""
+    import os
+    lib = _lib.lib()
+    binnr = int(binnr)
+    if not 1 <= binnr <= lib.ast_pairwise_max_bins():
+        raise ValueError(f"binnr={binnr}: 1..{lib.ast_pairwise_max_bins()} bins")
+    p = as_device(pos)
+    v = as_device(vel_cart_or_ang)
+    p = p if p.dtype in _REAL else p.to(torch.float64)
+    v = v if v.dtype in _REAL else v.to(torch.float64)
+    n = p.shape[0] if p.dim() == 2 else -1
+    if p.shape != (n, 3) or v.dim() != 2 or v.shape[0] != n or v.shape[1] not in (2, 3):
+        raise ValueError(f"pos must be (N, 3) and velocities (N, 2) or (N, 3), got {tuple(p.shape)} and {tuple(v.shape)}")
+    th1 = th2 = None
+    mode = 0
+    if theta1 is not None and v.shape[1] == 2:
+        th1, th2 = as_device(theta1, torch.float64).reshape(-1), as_device(theta2, torch.float64).reshape(-1)
+        if th1.numel() != n or th2.numel() != n:
+            raise ValueError("theta1 / theta2 need one angle per object")
+        tmax = (theta1.max().item() if isinstance(theta1, torch.Tensor) else np.max(theta1)) if n else 0.0
+        mode = 2 if tmax > 2 * np.pi else 1
+    single = os.environ.get("ASTRILD_PV_CELLS", "1") == "0"
+    ws_bytes = lib.ast_pairwise_workspace_bytes(n, binnr)
+    work = torch.empty(ws_bytes, dtype=torch.uint8, device=p.device)
+    nom = torch.empty(binnr, dtype=torch.float64, device=p.device)
+    denom = torch.empty(binnr, dtype=torch.float64, device=p.device)
+    counts = torch.empty(binnr, dtype=torch.int64, device=p.device)
+    s = stream()
+    check(lib.ast_pairwise_tv_prepare(ptr(p), real_code(p), ptr(v), real_code(v), v.shape[1], ptr(th1), ptr(th2), mode,
+                                      n, ptr(work), ws_bytes, s), "ast_pairwise_tv_prepare")
+    check(lib.ast_pairwise_tv(ptr(work), ws_bytes, n, binnr, float(binwidth), int(single), ptr(nom), ptr(denom),
+                              ptr(counts), s), "ast_pairwise_tv")
+    return nom, denom, counts

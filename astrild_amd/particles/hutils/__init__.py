@@ -1,1 +1,2 @@
 from .stats_subfind import SubFind  # noqa: F401
+from .mean_pairwise_velocity import make_rsep, make_rsep_uneven_bins, mean_pv_from_tv  # noqa: F401

@@ -771,6 +771,35 @@ int ast_convolve2d(const double* img_d, const double* window_d, double* out_d, i
 int ast_aperture_photometry(const double* img_d, double* out_d, double* work_d, int npix, double alpha_pix,
                             void* stream);
 
+/* ------------------------------------------------- mean pairwise velocity */
+
+/* Mean pairwise velocity from transverse velocities (Yasini et al. 2018), the estimator of
+ * particles/hutils/mean_pairwise_velocity.py: mean_pv_from_tv (:16-118) with the pair loop of pairwise_one_row
+ * (:121-176), and the BallTree pair finder of particles/utils_cython/pairwise_velocity.pyx.  No object cap (the
+ * reference asserts N <= 50000).  Two calls on one workspace of ast_pairwise_workspace_bytes(n, binnr) bytes
+ * (0: binnr outside 1..ast_pairwise_max_bins()):
+ *
+ * ast_pairwise_tv_prepare: per object, in fp64, r (pos_d (n, 3), pos_dtype widened), u = r / |r| and the cartesian
+ * transverse velocity t = J^T (0, v1, v2), J = get_sph_to_cart_jacobian(th = theta2, ph = theta1)
+ * (utils/geometrical_transforms.py:94-105), from vel_d (n, 2), vel_dtype; vel_ncomp = 3: vel_d is t itself (n, 3).
+ * angle_mode 0: theta1 = arctan(x / z), theta2 = arctan(y / z) (angular_coordinate_in_lc), both + 10 deg, as the
+ * reference does; 1: theta1_d / theta2_d (fp64, n) in radians; 2: in degrees.  Also the bounding box of r.
+ *
+ * ast_pairwise_tv: for every pair i != j with b = int(|r_i - r_j| / binwidth) < binnr (binnr = len(bins), the
+ * reference's count, reach binnr * binwidth), with p = (r_i - r_j) / |r_i - r_j| and
+ * q = (2 p - u_i (p.u_i) - u_j (p.u_j)) / 2:  nom_d[b] += (t_i - t_j).q, denom_d[b] += q.q, counts_d[b] += 1
+ * (outputs are written, not accumulated; all zero for n < 2).  Coincident objects add NaN to bin 0, like the
+ * reference.  Pair finder: a uniform cell grid of cells >= the reach over the bounding box (non-periodic);
+ * single_cell != 0 forces one cell (all pairs).  The sums are not bit-reproducible from call to call (LDS atomics);
+ * the counts are exact.  n < 2^31. */
+size_t ast_pairwise_workspace_bytes(size_t n, int binnr);
+int ast_pairwise_max_bins(void);
+int ast_pairwise_tv_prepare(const void* pos_d, int pos_dtype, const void* vel_d, int vel_dtype, int vel_ncomp,
+                            const double* theta1_d, const double* theta2_d, int angle_mode, size_t n, void* work_d,
+                            size_t work_bytes, void* stream);
+int ast_pairwise_tv(void* work_d, size_t work_bytes, size_t n, int binnr, double binwidth, int single_cell,
+                    double* nom_d, double* denom_d, unsigned long long* counts_d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
