@@ -151,6 +151,10 @@ SIGNATURES = {
     "ast_pairwise_max_bins": (_i, []),
     "ast_pairwise_tv_prepare": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _sz, _vp, _sz, _vp]),
     "ast_pairwise_tv": (_i, [_vp, _sz, _sz, _i, _d, _i, _vp, _vp, _vp, _vp]),
+    "ast_tpcf_workspace_bytes": (_sz, [_sz, _i, _i]),
+    "ast_tpcf_max_bins": (_i, []),
+    "ast_tpcf_prepare": (_i, [_vp, _i, _vp, _i, _i, _d, _sz, _vp, _sz, _vp, _vp]),
+    "ast_tpcf_pair_counts": (_i, [_vp, _sz, _sz, _d, _i, _vp, _i, _vp, _i, _i, _vp, _vp]),
 }
 
 _lib = None

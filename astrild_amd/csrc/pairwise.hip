@@ -3,6 +3,7 @@
 // pair finder, a tiled pair kernel with per-workgroup LDS histograms, and a fixed-order sum of the workgroup rows.
 // All pair arithmetic is fp64 (the library is built with -ffp-contract=off: op-by-op IEEE, like numpy).
 #include "ast_common.h"
+#include "cell_grid.h"
 #include <cmath>
 
 namespace {
@@ -10,7 +11,6 @@ namespace {
 constexpr int PV_BLOCK = 256;               // i objects per tile = j objects per LDS stage
 constexpr int PV_WAVES = PV_BLOCK / 64;
 constexpr int PV_GRID = 1024;               // persistent pair-kernel workgroups (256 CUs x 4)
-constexpr int PV_NEIGH = 14;                // the cell itself + 13 half-shell neighbours
 constexpr size_t PV_MAX_CELLS = size_t(1) << 20;
 constexpr int PV_MAX_BINS = 480;            // 4 wave histograms x 24 B x bins + the j stage fit 64 KiB of LDS
 
@@ -23,7 +23,6 @@ struct PvParams {
     unsigned ncells, ntiles;
 };
 
-inline size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
 inline size_t cells_cap(size_t n) { return n < 1 ? 1 : (n < PV_MAX_CELLS ? n : PV_MAX_CELLS); }
 
 struct PvLayout {
@@ -43,23 +42,6 @@ struct PvLayout {
         total = o;
     }
 };
-
-__device__ inline unsigned long long d2key(double d) {
-    unsigned long long u = (unsigned long long)__double_as_longlong(d);
-    return (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
-}
-__device__ inline double key2d(unsigned long long k) {
-    unsigned long long u = (k & 0x8000000000000000ull) ? (k & 0x7fffffffffffffffull) : ~k;
-    return __longlong_as_double((long long)u);
-}
-__device__ inline double wave_min(double v) {
-    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ inline double wave_max(double v) {
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
 
 // One thread per object: r (widened to fp64), u = r / |r|, and the cartesian transverse velocity
 // t = J(th = theta2, ph = theta1)^T (0, v1, v2) of get_sph_to_cart_jacobian (or v itself when 3 components are given).
@@ -180,62 +162,6 @@ pv_count_kernel(const PvObj* __restrict__ obj, size_t n, const PvParams* prm, un
     }
 }
 
-// One workgroup of 1024: exclusive scans of the cell counts (-> cell_start, cursor) and of the tiles per cell,
-// ceil(count / PV_BLOCK) (-> tile_start); ntiles = the total.  Each thread scans a contiguous chunk.
-__global__ void __launch_bounds__(1024)
-pv_scan_kernel(const unsigned* __restrict__ cnt, PvParams* prm, unsigned* __restrict__ cell_start,
-               unsigned* __restrict__ tile_start, unsigned* __restrict__ cursor) {
-    __shared__ unsigned s_obj[1024], s_til[1024];
-    const unsigned nc = prm->ncells;
-    const unsigned chunk = (nc + 1023) / 1024;
-    const unsigned c0 = threadIdx.x * chunk, c1 = min(nc, c0 + chunk);
-    unsigned so = 0, st = 0;
-    for (unsigned c = c0; c < c1; ++c) { so += cnt[c]; st += (cnt[c] + PV_BLOCK - 1) / PV_BLOCK; }
-    s_obj[threadIdx.x] = so;
-    s_til[threadIdx.x] = st;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned ao = 0, at = 0;
-        for (int k = 0; k < 1024; ++k) {
-            const unsigned vo = s_obj[k], vt = s_til[k];
-            s_obj[k] = ao; s_til[k] = at;
-            ao += vo; at += vt;
-        }
-        cell_start[nc] = ao;
-        tile_start[nc] = at;
-        prm->ntiles = at;
-    }
-    __syncthreads();
-    so = s_obj[threadIdx.x];
-    st = s_til[threadIdx.x];
-    for (unsigned c = c0; c < c1; ++c) {
-        cell_start[c] = so;
-        cursor[c] = so;
-        tile_start[c] = st;
-        so += cnt[c];
-        st += (cnt[c] + PV_BLOCK - 1) / PV_BLOCK;
-    }
-}
-
-__global__ void __launch_bounds__(256)
-pv_scatter_kernel(const PvObj* __restrict__ obj, size_t n, const unsigned* __restrict__ cell_of,
-                  unsigned* __restrict__ cursor, PvObj* __restrict__ sorted) {
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const unsigned slot = atomicAdd(&cursor[cell_of[i]], 1u);
-        sorted[slot] = obj[i];
-    }
-}
-
-__constant__ int pv_offsets[PV_NEIGH][3] = {
-    {0, 0, 0},
-    {1, 0, 0},
-    {-1, 1, 0}, {0, 1, 0}, {1, 1, 0},
-    {-1, -1, 1}, {0, -1, 1}, {1, -1, 1},
-    {-1, 0, 1}, {0, 0, 1}, {1, 0, 1},
-    {-1, 1, 1}, {0, 1, 1}, {1, 1, 1},
-};
-
 // Work item = (tile of PV_BLOCK objects of cell a, neighbour k): each thread holds one i of the tile, the j objects of
 // cell a + offset[k] pass through LDS PV_BLOCK at a time (k = 0: the cell itself, j > i only).  A persistent grid walks
 // the items with a fixed stride; each wave adds into its own LDS histogram (nom, denom, pairs), and at the end the
@@ -257,18 +183,13 @@ pv_pair_kernel(const PvObj* __restrict__ sorted, const unsigned* __restrict__ ce
 
     const int dx = prm->dims[0], dy = prm->dims[1], dz = prm->dims[2];
     const unsigned ncells = prm->ncells;
-    const unsigned long long nitems = (unsigned long long)prm->ntiles * PV_NEIGH;
+    const unsigned long long nitems = (unsigned long long)prm->ntiles * GRID_NEIGH;
     for (unsigned long long item = blockIdx.x; item < nitems; item += gridDim.x) {
-        const unsigned tile = (unsigned)(item / PV_NEIGH);
-        const int k = (int)(item % PV_NEIGH);
-        unsigned lo = 0, hi = ncells;                   // tile_start[lo] <= tile < tile_start[hi]
-        while (hi - lo > 1) {
-            const unsigned mid = (lo + hi) / 2;
-            if (tile_start[mid] <= tile) lo = mid; else hi = mid;
-        }
-        const unsigned a = lo;
+        const unsigned tile = (unsigned)(item / GRID_NEIGH);
+        const int k = (int)(item % GRID_NEIGH);
+        const unsigned a = grid_cell_of_tile(tile_start, ncells, tile);
         const int ax = (int)(a % (unsigned)dx), ay = (int)((a / (unsigned)dx) % (unsigned)dy), az = (int)(a / ((unsigned)dx * (unsigned)dy));
-        const int bx = ax + pv_offsets[k][0], by = ay + pv_offsets[k][1], bz = az + pv_offsets[k][2];
+        const int bx = ax + grid_offsets[k][0], by = ay + grid_offsets[k][1], bz = az + grid_offsets[k][2];
         if (bx < 0 || bx >= dx || by < 0 || by >= dy || bz < 0 || bz >= dz) continue;
         const unsigned b = ((unsigned)bz * (unsigned)dy + (unsigned)by) * (unsigned)dx + (unsigned)bx;
         const unsigned i0 = cell_start[a] + (tile - tile_start[a]) * PV_BLOCK;
@@ -436,9 +357,9 @@ extern "C" int ast_pairwise_tv(void* work_d, size_t work_bytes, size_t n, int bi
         AST_CHECK_HIP(hipMemsetAsync(cnt, 0, cap * 4, s));
         pv_count_kernel<<<ast::stream_grid(n, 256), 256, 0, s>>>(obj, n, prm, cell_of, cnt);
         AST_CHECK_LAUNCH();
-        pv_scan_kernel<<<1, 1024, 0, s>>>(cnt, prm, cell_start, tile_start, cursor);
+        grid_scan_kernel<PV_BLOCK><<<1, 1024, 0, s>>>(cnt, prm, cell_start, tile_start, cursor);
         AST_CHECK_LAUNCH();
-        pv_scatter_kernel<<<ast::stream_grid(n, 256), 256, 0, s>>>(obj, n, cell_of, cursor, sorted);
+        grid_scatter_kernel<<<ast::stream_grid(n, 256), 256, 0, s>>>(obj, n, cell_of, cursor, sorted);
         AST_CHECK_LAUNCH();
     }
     // Pre-test on d^2 with a relative margin far above the rounding of d and d / binwidth: every pair whose

@@ -1166,3 +1166,72 @@ def pairwise_tv(pos, vel_cart_or_ang, binnr, binwidth, theta1=None, theta2=None)
     check(lib.ast_pairwise_tv(ptr(work), ws_bytes, n, binnr, float(binwidth), int(single), ptr(nom), ptr(denom),
                               ptr(counts), s), "ast_pairwise_tv")
     return nom, denom, counts
+
+
+# ------------------------------------------------------------------ two-point correlation function
+def check_tpcf_edges(s_edges, mu_edges, boxsize):
+    """halotools' argument checks of a periodic (s, mu) pair count, on the host: fp64 edges ``(s, mu)`` (``mu`` None
+    stays None) or ValueError.  s edges strictly increasing, >= 0, max < boxsize / 3; mu edges strictly increasing
+    within [0, 1]; at most ``ast_tpcf_max_bins()`` bins."""
+    boxsize = float(boxsize)
+    if not (np.isfinite(boxsize) and boxsize > 0):
+        raise ValueError(f"boxsize must be positive and finite, got {boxsize}")
+    s = np.asarray(s_edges, dtype=np.float64).reshape(-1)
+    if len(s) < 2 or not np.all(np.isfinite(s)) or np.any(np.diff(s) <= 0) or s[0] < 0:
+        raise ValueError("s edges must be at least two finite, non-negative, strictly increasing values")
+    if not s[-1] < boxsize / 3.0:
+        raise ValueError(f"the largest s edge ({s[-1]}) must be below boxsize / 3 ({boxsize / 3.0})")
+    mu = None
+    if mu_edges is not None:
+        mu = np.asarray(mu_edges, dtype=np.float64).reshape(-1)
+        if len(mu) < 2 or not np.all(np.isfinite(mu)) or np.any(np.diff(mu) <= 0) or not (mu[0] >= 0 and mu[-1] <= 1):
+            raise ValueError("mu edges must be at least two strictly increasing values within [0, 1]")
+    ns, nmu = len(s) - 1, 0 if mu is None else len(mu) - 1
+    if ns > 1000 or nmu > 1000 or ns * max(nmu, 1) > _lib.lib().ast_tpcf_max_bins():
+        raise ValueError(f"{ns} x {nmu} bins: at most 1000 edges per axis and {_lib.lib().ast_tpcf_max_bins()} bins")
+    return s, mu
+
+
+def tpcf_pair_counts(pos, boxsize, s_edges, mu_edges=None, vel=None, los=2):
+    """Unordered pair counts of a periodic box for the two-point correlation function (particles/hutils/tpcf.py):
+    an int64 device tensor, (ns, nmu) with ``mu_edges``, else (ns,).  ``vel`` given: the redshift-space shift
+    pos[:, los] += vel[:, los] / 100 and one wrap into [0, boxsize], in the input dtypes (tpcf.py:74-97).  Minimum image
+    per axis; a pair counts in (k, l) when s_k^2 < d^2 <= s_{k+1}^2 and mu_l < mu <= mu_{l+1}, mu = |d_los| / d.
+    ``pos`` / ``vel``: (N, 3), numpy arrays or device tensors, float32 or float64.  ValueError (before any GPU work)
+    for bad edges or ``los``, and (from the device bounds) for shifted positions outside [0, boxsize].
+    ASTRILD_TPCF_CELLS=0 forces one cell (all pairs) instead of the cell grid."""
+    import os
+    s, mu = check_tpcf_edges(s_edges, mu_edges, boxsize)
+    if los not in (0, 1, 2):
+        raise ValueError(f"los must be 0, 1 or 2, got {los}")
+    boxsize = float(boxsize)
+    lib = _lib.lib()
+    p = as_device(pos)
+    p = p if p.dtype in _REAL else p.to(torch.float64)
+    n = p.shape[0] if p.dim() == 2 else -1
+    if p.shape != (n, 3):
+        raise ValueError(f"pos must be (N, 3), got {tuple(p.shape)}")
+    v = None
+    if vel is not None:
+        v = as_device(vel)
+        v = v if v.dtype in _REAL else v.to(torch.float64)
+        if v.shape != (n, 3):
+            raise ValueError(f"vel must be (N, 3) like pos, got {tuple(v.shape)}")
+    ns, nmu = len(s) - 1, 0 if mu is None else len(mu) - 1
+    single = os.environ.get("ASTRILD_TPCF_CELLS", "1") == "0"
+    ws_bytes = lib.ast_tpcf_workspace_bytes(n, ns, nmu)
+    work = torch.empty(ws_bytes, dtype=torch.uint8, device=p.device)
+    bounds = torch.empty(6, dtype=torch.float64, device=p.device)
+    st = stream()
+    check(lib.ast_tpcf_prepare(ptr(p), real_code(p), ptr(v), real_code(v) if v is not None else F64, los, boxsize, n,
+                               ptr(work), ws_bytes, ptr(bounds), st), "ast_tpcf_prepare")
+    b = to_numpy(bounds)
+    if n and not (np.all(b[:3] >= 0.0) and np.all(b[3:] <= boxsize)):
+        raise ValueError(f"positions (after the redshift-space shift) must lie in [0, {boxsize}]: "
+                         f"min {b[:3].tolist()}, max {b[3:].tolist()}")
+    s_d = as_device(s)
+    mu_d = as_device(mu) if mu is not None else None
+    counts = torch.empty((ns, nmu) if nmu else (ns,), dtype=torch.int64, device=p.device)
+    check(lib.ast_tpcf_pair_counts(ptr(work), ws_bytes, n, boxsize, los, ptr(s_d), ns, ptr(mu_d), nmu, int(single),
+                                   ptr(counts), st), "ast_tpcf_pair_counts")
+    return counts

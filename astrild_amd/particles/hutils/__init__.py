@@ -1,2 +1,3 @@
 from .stats_subfind import SubFind  # noqa: F401
 from .mean_pairwise_velocity import make_rsep, make_rsep_uneven_bins, mean_pv_from_tv  # noqa: F401
+from .tpcf import TPCF, tpcf_multipole, tpcf_r  # noqa: F401

@@ -800,6 +800,33 @@ int ast_pairwise_tv_prepare(const void* pos_d, int pos_dtype, const void* vel_d,
 int ast_pairwise_tv(void* work_d, size_t work_bytes, size_t n, int binnr, double binwidth, int single_cell,
                     double* nom_d, double* denom_d, unsigned long long* counts_d, void* stream);
 
+/* ------------------------------------------------- two-point correlation function */
+
+/* Pair counts of the two-point correlation function of a periodic box: particles/hutils/tpcf.py (TPCF.compute /
+ * TPCF.tpcf_s, :18-111), which calls halotools' s_mu_tpcf (and, commented out in halo.py / stats_subfind.py, its real-
+ * space tpcf).  Two calls on one workspace of ast_tpcf_workspace_bytes(n, ns, nmu) bytes (0: ns outside 1..1000, nmu
+ * outside 0..1000 or ns * max(nmu, 1) > ast_tpcf_max_bins()):
+ *
+ * ast_tpcf_prepare: per object, the redshift-space shift of tpcf.py:74-97 in the input dtypes, as numpy does it:
+ * pos[los] += vel[los] / 100 (vel / 100 in vel_dtype, the add in the wider dtype, stored as pos_dtype), then
+ * > boxsize -> - boxsize, < 0 -> + boxsize (in pos_dtype); vel_d == NULL: no shift and no wrap.  pos_d, vel_d (n, 3).
+ * The shifted positions are widened to fp64 into the workspace, and bounds_d[6] receives their min (x, y, z) and
+ * max (x, y, z) (NaN counts as out of range; (+inf, -inf) for n == 0) so the caller can check [0, boxsize].
+ *
+ * ast_tpcf_pair_counts: for every unordered pair i < j, with the minimum image a = min(|dx|, boxsize - |dx|) per
+ * axis, d2 = (a_x^2 + a_y^2) + a_z^2 and mu = a_los / sqrt(d2) (fp64): the pair counts in bin (k, l) when
+ * s_k^2 < d2 <= s_{k+1}^2 (s_edges_d: ns + 1 edges, squared in fp64) and mu_l < mu <= mu_{l+1} (mu_edges_d: nmu + 1
+ * edges; nmu = 0: no mu test).  counts_d[k * max(nmu, 1) + l] (written, not accumulated; zero for n < 2) is exact for
+ * n < 2^31.  Pair finder: a periodic cell grid of cells at least the top s edge wide, at least 3 per axis (one cell
+ * when the top edge is >= boxsize / 3); single_cell != 0 forces one cell (all pairs, minimum image still applied). */
+size_t ast_tpcf_workspace_bytes(size_t n, int ns, int nmu);
+int ast_tpcf_max_bins(void);
+int ast_tpcf_prepare(const void* pos_d, int pos_dtype, const void* vel_d, int vel_dtype, int los, double boxsize,
+                     size_t n, void* work_d, size_t work_bytes, double* bounds_d, void* stream);
+int ast_tpcf_pair_counts(void* work_d, size_t work_bytes, size_t n, double boxsize, int los, const double* s_edges_d,
+                         int ns, const double* mu_edges_d, int nmu, int single_cell, unsigned long long* counts_d,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif
