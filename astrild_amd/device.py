@@ -1235,3 +1235,46 @@ def tpcf_pair_counts(pos, boxsize, s_edges, mu_edges=None, vel=None, los=2):
     check(lib.ast_tpcf_pair_counts(ptr(work), ws_bytes, n, boxsize, los, ptr(s_d), ns, ptr(mu_d), nmu, int(single),
                                    ptr(counts), st), "ast_tpcf_pair_counts")
     return counts
+
+
+def annulus_profiles(skymap, x_pix, y_pix, rad_pix, extend, nbins, delta_eta=None):
+    """Per-annulus sums and pixel counts of objects on a 2D map (profiles/profile_2d.py: from_map / profiling): device
+    tensors ``(sums, counts)``, (N, nbins) float64 and int64, the true sums and counts (not the reference's count
+    alignment, which ``profile_2d.aligned_values`` applies).  Object i reads skymap[y + a, x + b] for -R <= a, b < R,
+    R = ceil(r * extend), into bin eta = int(sqrt(a^2 + b^2) / r / delta_eta) when eta < nbins, with r, x, y truncated
+    to integers and delta_eta = extend / nbins unless given; negative indices wrap as numpy's do.  The bins are decided
+    on the host with exact integer thresholds (``profile_2d.annulus_geometry``), which also raises IndexError /
+    ValueError before any GPU work.  ``skymap``: a 2D numpy array or device tensor, float32 or float64.
+    ASTRILD_PROFILE_BANDS=0 makes each object one work item instead of bands of rows."""
+    import os
+    from .profiles import profile_2d as p2d
+    lib = _lib.lib()
+    shape = tuple(skymap.shape)
+    if len(shape) != 2 or shape[0] < 1 or shape[1] < 1:
+        raise ValueError(f"skymap must be a non-empty 2D map, got shape {shape}")
+    if int(nbins) == nbins and not 1 <= nbins <= lib.ast_profile2d_max_bins():
+        raise ValueError(f"nbins must be in 1..{lib.ast_profile2d_max_bins()}, got {nbins}")
+    y, x, R, m, T = p2d.annulus_geometry(shape, x_pix, y_pix, rad_pix, extend, nbins, delta_eta)
+    nbins = int(nbins)
+    t = as_device(skymap)
+    t = t if t.dtype in _REAL else t.to(torch.float64)
+    n = len(R)
+    rows = m + np.minimum(m, R - 1) + 1
+    bands = os.environ.get("ASTRILD_PROFILE_BANDS", "1") != "0"
+    band_rows = lib.ast_profile2d_band_rows() if bands else 0
+    per_obj = -(-rows // band_rows) if bands else np.ones(n, dtype=np.int64)
+    item_start = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(per_obj, out=item_start[1:])
+    n_work = int(item_start[-1])
+    centres = as_device(np.stack([y, x], axis=1))
+    reach = as_device(np.stack([R, m], axis=1))
+    thr = as_device(np.ascontiguousarray(T, dtype=np.int64))
+    starts = as_device(item_start)
+    ws_bytes = lib.ast_profile2d_workspace_bytes(n, n_work, nbins)
+    work = torch.empty(ws_bytes, dtype=torch.uint8, device=t.device)
+    sums = torch.empty((n, nbins), dtype=torch.float64, device=t.device)
+    counts = torch.empty((n, nbins), dtype=torch.int64, device=t.device)
+    check(lib.ast_profile2d(ptr(t), real_code(t), shape[0], shape[1], n, ptr(centres), ptr(reach), ptr(thr), nbins,
+                            band_rows, ptr(starts), n_work, ptr(work), ws_bytes, ptr(sums), ptr(counts), stream()),
+          "ast_profile2d")
+    return sums, counts

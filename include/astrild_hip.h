@@ -827,6 +827,29 @@ int ast_tpcf_pair_counts(void* work_d, size_t work_bytes, size_t n, double boxsi
                          int ns, const double* mu_edges_d, int nmu, int single_cell, unsigned long long* counts_d,
                          void* stream);
 
+/* ------------------------------------------------- radial profiles on 2D maps */
+
+/* Annulus sums and counts of objects on a 2D map: profiles/profile_2d.py (from_map, :10-59, and profiling, :92-153),
+ * which rays/void.py (Voids.get_profiles / get_profile_stats, :188-410) and rays/peak.py (:95-239) call.  map_d: a
+ * row-major (ny, nx) map of dtype AST_F32 / AST_F64, widened to fp64 on load.  Per object o: centres_d[2o] = y,
+ * [2o + 1] = x (pixel indices, truncated by the host); reach_d[2o] = R = ceil(r * extend), [2o + 1] = m, the read reach;
+ * thresholds_d[o * nbins + k - 1] = T_k, k = 1..nbins, the least d2 = a^2 + b^2 whose annulus index is >= k (2R^2 + 1
+ * when none).  Pixel (a, b), -R <= a, b < R, adds map[y + a][x + b] to bin k when T_k <= d2 < T_{k+1} (T_0 = 0) and is
+ * read when d2 < T_nbins; an index below 0 wraps once, as numpy's negative indices do.  The host must have checked
+ * -ny <= y - m and y + min(m, R - 1) < ny (x likewise against nx); an object outside gets NaN sums and count -1.
+ * Work items are bands of band_rows rows (ast_profile2d_band_rows(); 0: one item per object): object o owns items
+ * item_start_d[o] .. item_start_d[o + 1] - 1 (item_start_d[0] = 0, item_start_d[n_obj] = n_work).  sums_d / counts_d
+ * (n_obj, nbins) fp64 / int64 are written: the true per-annulus sums and pixel counts, each sum formed in an order fixed
+ * by the object's geometry (bit-identical between calls).  The workspace holds the band rows: ast_profile2d_workspace_
+ * bytes(n_obj, n_work, nbins) bytes (0: nbins outside 1..ast_profile2d_max_bins() or n_work < n_obj). */
+int ast_profile2d_max_bins(void);
+int ast_profile2d_band_rows(void);
+size_t ast_profile2d_workspace_bytes(size_t n_obj, size_t n_work, int nbins);
+int ast_profile2d(const void* map_d, int dtype, size_t ny, size_t nx, size_t n_obj, const long long* centres_d,
+                  const long long* reach_d, const long long* thresholds_d, int nbins, int band_rows,
+                  const long long* item_start_d, size_t n_work, void* work_d, size_t work_bytes, double* sums_d,
+                  long long* counts_d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
