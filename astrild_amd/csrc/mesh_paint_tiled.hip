@@ -971,7 +971,7 @@ scatter_level_b_kernel(const T* __restrict__ staging, const unsigned long long* 
                 if (lslot[u] == 0xffffffffu) continue;
                 const unsigned long long k = late_base + lslot[u];
                 if (k < late_cap) reinterpret_cast<vec4_t*>(late_list)[k] = vec4_t{x[u], y[u], z[u], m[u]};
-                else if (dropped) atomicAdd(dropped, 1ull);            // more than a quarter of all particles: reported, not lost silently
+                else if (dropped) atomicAdd(dropped, 1ull);            // beyond late_capacity(): reported, not lost silently
             }
         }
         staged_store<T, SW, NT>(x, y, z, m, where, lstart, base, room, total, strays, stage, sidx);
@@ -1888,6 +1888,10 @@ struct Workspace {
 
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
+// Records {x, y, z, m} the scatter path's late list holds: it lives in the single pass's overflow list (np x 4 bytes), so
+// np / 4 at float32 and np / 8 at float64.  What does not fit is counted as dropped (device.paint repaints two-pass).
+inline unsigned long long late_capacity(size_t np, size_t esz) { return np / 4 * sizeof(uint32_t) / esz; }
+
 // Single pass: every tile gets room for twice the mean occupancy (at least mean + 512).
 inline uint32_t tile_capacity(size_t np, uint32_t ntiles) {
     const size_t mean = (np + ntiles - 1) / ntiles;
@@ -1952,7 +1956,7 @@ Workspace carve(void* base, size_t np, uint32_t ntiles, uint32_t ncols, int flag
     w.strays = take((size_t)ntiles * w.scap * 4 * esz);
     w.staging = take(w.tpb ? (size_t)w.nb * SC_GROUPS * w.cap_bg * 4 * esz : 0);
     w.ovf = (uint32_t*)take(two_pass ? 0 : np * 4);
-    w.late_index = (uint32_t*)take(w.tpb ? np / 4 * sizeof(uint32_t) / esz * 4 : 0);      // one id per record the list has room for
+    w.late_index = (uint32_t*)take(w.tpb ? late_capacity(np, esz) * sizeof(uint32_t) : 0);      // one id per record the list has room for
     w.rec = take(rec_bytes);
     w.zrec = (unsigned long long*)take(zrec_bytes);
     w.bytes = off;
@@ -2074,7 +2078,7 @@ int run_tiled(const T* pos, const T* mass, size_t np, TileGeom g, uint32_t ntile
                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b_max));
                 attr_once.mark();
             }
-            const unsigned long long late_cap = np / 4 * sizeof(uint32_t) / sizeof(T);       // the overflow list's room
+            const unsigned long long late_cap = late_capacity(np, sizeof(T));       // the overflow list's room
             {
                 AST_PROF("paint_tiled.level_a", s);
                 scatter_level_a_kernel<T, W, PX, SW><<<nchunks, SCA_THREADS, lds_a, s>>>(
@@ -2160,7 +2164,7 @@ int run_tiled(const T* pos, const T* mass, size_t np, TileGeom g, uint32_t ntile
             AST_PROF("paint_tiled.overflow", s);
             const int x_lo = sel.row0 * TX, x_hi = std::min(g.nx_alloc, (sel.row0 + sel.nrows) * TX);
             if (w.tpb)
-                late_deposit_kernel<T, W><<<128, 256, 0, s>>>((const T*)w.ovf, w.late, np / 4 * sizeof(uint32_t) / sizeof(T), g, scale, grid, dropped, x_lo, x_hi);
+                late_deposit_kernel<T, W><<<128, 256, 0, s>>>((const T*)w.ovf, w.late, late_capacity(np, sizeof(T)), g, scale, grid, dropped, x_lo, x_hi);
             else
                 overflow_deposit_kernel<T, W><<<128, 256, 0, s>>>(pos, mass, w.ovf, w.ovf_count, g, scale, grid, dropped, x_lo, x_hi);
         } else {
@@ -2196,8 +2200,12 @@ int run_tiled(const T* pos, const T* mass, size_t np, TileGeom g, uint32_t ntile
         // of its own - counted per tile, scanned, its record numbers filled tile-major, then ONE workgroup per tile adds its
         // records up in LDS and flushes the tile onto the grid: the two-pass variant with the list's records as particles.
         // The list's length stays on the device: all kernels are launched, each looks at the count.
-        const unsigned long long late_cap = np / 4 * sizeof(uint32_t) / sizeof(T);
-        const unsigned long long lds_min = getenv("AST_PAINT_LATE_LDS_MIN") ? strtoull(getenv("AST_PAINT_LATE_LDS_MIN"), nullptr, 10) : 262144ull;
+        const unsigned long long late_cap = late_capacity(np, sizeof(T));
+        // (float32: any non-empty list.  Thousands of fp32 atomics on one blob cell, each rounded in arrival order, put it up
+        // to 7.6e-6 of the grid's maximum off the exact sum at 128^3 - beyond the 3e-6 the paint is held to; the LDS sums in
+        // double round once.  An empty list costs the same either way: every kernel reads the count and returns.)
+        const unsigned long long lds_min = getenv("AST_PAINT_LATE_LDS_MIN") ? strtoull(getenv("AST_PAINT_LATE_LDS_MIN"), nullptr, 10)
+                                                                            : sizeof(T) == 4 ? 1ull : 262144ull;
         late_deposit_kernel<T, W><<<1024, 256, 0, s>>>((const T*)w.ovf, w.late, late_cap, g, scale, grid, dropped, 0, g.nx_alloc, lds_min);
         if (lds_min != ~0ull && late_cap > 0) {
             const size_t lint = (late_cap + per_interval - 1) / per_interval;
@@ -2325,6 +2333,11 @@ extern "C" int ast_debug_stamps(unsigned long long* stamps_host, unsigned* count
     return AST_OK;
 }
 #endif
+
+extern "C" size_t ast_paint_scatter_late_capacity(int dtype, size_t np) {
+    if (dtype != AST_F32 && dtype != AST_F64) return 0;
+    return (size_t)late_capacity(np, dtype == AST_F32 ? 4 : 8);
+}
 
 extern "C" size_t ast_paint_tiled_workspace_bytes(int window, int dtype, size_t np, int nmesh, int nx_alloc, int flags) {
     TileGeom g;

@@ -241,6 +241,19 @@ def probe_input(pos, nmesh, boxsize, shift=0.0, windows=256):
             "mean_tile": npart / ntiles, "samples": samples}
 
 
+def scatter_late_capacity(dtype, npart):
+    """Records the late list of the bucket scatter (AST_PAINT_SCATTERED) holds for ``npart`` particles of ``dtype``:
+    npart / 4 at float32, npart / 8 at float64 (ast_paint_scatter_late_capacity, host only)."""
+    return int(_lib.lib().ast_paint_scatter_late_capacity(_REAL[dtype], int(npart)))
+
+
+def scatter_overflow_limit(dtype, npart):
+    """The largest estimated overflow (:func:`probe_input`) for which ``paint`` takes the bucket scatter: four fifths of
+    the late list (npart / 5 at float32, npart / 10 at float64).  The late list also takes what level A's bucket segments
+    cannot hold, so it fills beyond the estimate; what still does not fit is repainted two-pass."""
+    return scatter_late_capacity(dtype, npart) * 4 // 5
+
+
 def synth_clustered_particles(npside, nmesh, boxsize, seed=20240601, sigma_cells=0.5, nattractors=256, amplitude=0.95,
                               shuffle=False, dtype=torch.float32):
     """A clustered synthetic set (ast_synth_clustered_particles): the lattice collapsing onto ``nattractors`` centres - tile
@@ -367,14 +380,16 @@ def paint(pos, mass, nmesh, boxsize, window="cic", scale=1.0, out=None, method="
         offset = total_mass(mass, npart) * float(scale) / float(n) ** 3
     off_planes = (0, -1) if offset_planes is None else offset_planes      # (first buffer plane, count) that get the offset
     compact = use_tiled and not accumulate and method != "tiled2"       # single pass + overwrite: group / stray lists
-    attempts, probed = 0, None
-    if compact and hint is None and npart >= (1 << 20) and nx == n and int(x_start) == 0:
+    attempts, probed, nd = 0, None, None
+    whole = nx == n and int(x_start) == 0
+    if compact and hint is None and npart >= (1 << 20) and whole:
         probed = probe_input(pos, n, boxsize, shift)                    # (a wrong guess costs time, never correctness)
-        if probed is not None and probed["groupable"] < 0.25 and probed["overflow"] <= npart // 5:
+        if probed is not None and probed["groupable"] < 0.25 and probed["overflow"] <= scatter_overflow_limit(pos.dtype, npart):
             # no spatial order in memory: the bucket scatter, clustered or not - the two-pass variant makes two global
             # atomics per particle on such input (1024^3 clustered + shuffled: 130 ms against 24); tiles that overflow
             # their segments go through the late list, reserved once per workgroup and chunk (the list holds a quarter of
-            # the particles: beyond a fifth estimated, the two-pass variant below, slow but without any capacity)
+            # the particles at float32, an eighth at float64: beyond four fifths of that estimated, the two-pass variant
+            # below, slow but without any capacity)
             tflags |= 8
         elif probed is not None and probed["overflow"] > npart // 64:
             tflags = (tflags & ~(8 | 16)) | 1                           # clustered, in file order: the exact two-pass variant at once
@@ -418,6 +433,19 @@ def paint(pos, mass, nmesh, boxsize, window="cic", scale=1.0, out=None, method="
                     compact = False
                 ws_bytes = int(L.ast_paint_tiled_workspace_bytes(win, code, npart, n, nx, tflags))
                 continue
+            if tflags & 8 and whole:
+                # nothing falls outside the whole periodic grid: a dropped deposit of the bucket scatter is a record its
+                # late list had no room for (more than the probe estimated, or a "scattered" hint) - never lost, never
+                # reported as outside the buffer: the exact two-pass lists paint it again (one 8-byte read)
+                nd = int(dropped.item())
+                if nd:
+                    dropped.zero_()
+                    nd = None
+                    del ws
+                    tflags = (tflags & ~8) | 1
+                    compact = False
+                    ws_bytes = int(L.ast_paint_tiled_workspace_bytes(win, code, npart, n, nx, tflags))
+                    continue
             if stats is not None:
                 stats.update(st or {}, scattered=bool(tflags & 8), attempts=attempts,
                              path="two-pass" if tflags & 1 else "scattered" if tflags & 8 else "single-pass")
@@ -428,7 +456,8 @@ def paint(pos, mass, nmesh, boxsize, window="cic", scale=1.0, out=None, method="
         check(L.ast_paint(win, code, ptr(pos), ptr(mass), npart, n, float(boxsize), float(scale),
                           int(x_start), nx, ptr(out), ptr(dropped), float(shift), stream()), "ast_paint")
     if check_dropped:
-        nd = int(dropped.item())
+        if nd is None:
+            nd = int(dropped.item())
         if nd:
             raise _lib.AstrildHipError(f"{nd} deposits fell outside the grid buffer "
                                        f"(x_start={x_start}, nx_alloc={nx})")

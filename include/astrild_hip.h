@@ -230,6 +230,10 @@ int ast_paint_tiled_halo(void* workspace_d, int window, int dtype, size_t np, in
  * AST_PAINT_SCATTERED or AST_PAINT_TWO_PASS. */
 int ast_paint_tiled_list_stats(void* workspace_d, int window, int dtype, size_t np, int nmesh, int nx_alloc, int flags,
                                unsigned long long* out_d, void* stream);
+/* Host only: the records {x, y, z, m} the AST_PAINT_SCATTERED paint's late list holds for np particles (np / 4 at
+ * AST_F32, np / 8 at AST_F64; 0 for another dtype).  Records beyond it are counted in dropped_d, not deposited: on a
+ * whole periodic grid a nonzero drop count after such a paint means the list ran out of room. */
+size_t ast_paint_scatter_late_capacity(int dtype, size_t np);
 /* Does the input have spatial order in memory?  `windows` (2 .. 65536) runs of 32 consecutive particles, evenly spread over
  * pos_d; *groupable_d (device, 4 bytes; zeroed by the call) = the number of runs in which at least 8 particles share the
  * 8 x 8 x 32-cell tile of the run's 16th particle - what the tiled paint's grouping kernel turns into group records.

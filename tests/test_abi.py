@@ -84,3 +84,28 @@ def test_order_probe_sample_stays_inside_the_particle_array():
     nat = torch.from_numpy((((ijk + 0.5 + 0.5 * rng.standard_normal(ijk.shape)) * (L / n)) % L).astype(np.float32))
     assert not dev.sample_is_unordered(nat, n, L)
     assert dev.sample_is_unordered(nat[torch.from_numpy(rng.permutation(len(nat)))].contiguous(), n, L)
+
+
+def test_scatter_probe_limit_stays_under_the_late_capacity():
+    """device.paint takes the bucket scatter up to an estimated overflow of scatter_overflow_limit: for every particle count
+    the tiled paint accepts (up to 2^32 - 66) and both dtypes that is below what the late list holds - the records
+    {x, y, z, m} that fit the single pass's overflow list of npart x 4 bytes - and, at float32, never above npart / 5, the
+    rule it replaced.  Host-only library calls."""
+    import numpy as np
+    import torch
+    from astrild_amd import _lib, device as dev
+    lib = _lib.lib()
+    counts = {1 << 20, (1 << 20) + 1, (1 << 20) + 7, 3 * 2 ** 20 + 5, 1 << 21, 1 << 24, (1 << 30) - 1, 1 << 30, 1 << 31,
+              (1 << 32) - 67, (1 << 32) - 66}
+    counts |= {int(v) for v in np.geomspace(1 << 20, (1 << 32) - 66, 97)}
+    counts |= {int(v) for v in np.random.default_rng(5).integers(1 << 20, (1 << 32) - 65, 200)}
+    for dtype, esz in ((torch.float32, 4), (torch.float64, 8)):
+        for npart in sorted(counts):
+            cap = dev.scatter_late_capacity(dtype, npart)
+            limit = dev.scatter_overflow_limit(dtype, npart)
+            assert cap == int(lib.ast_paint_scatter_late_capacity(_lib.F32 if esz == 4 else _lib.F64, npart))
+            assert cap * 4 * esz <= npart * 4 < (cap + 1) * 4 * esz, (dtype, npart, cap)
+            assert 0 < limit < cap and limit >= cap * 4 // 5, (dtype, npart, limit, cap)
+            if esz == 4:
+                assert limit <= npart // 5
+    assert lib.ast_paint_scatter_late_capacity(7, 1 << 20) == 0

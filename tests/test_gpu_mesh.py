@@ -742,8 +742,11 @@ def test_clustered_input_goes_to_the_two_pass_path_in_one_attempt(dev, shuffle):
     st = {}
     grid = dev.paint(pos, None, n, L, "cic", method="tiled", check_dropped=False, stats=st)
     # file order: the exact two-pass lists; no order in memory: the bucket scatter (its late list reserved per workgroup)
-    # (the late list holds a quarter of the particles: beyond a fifth estimated - this set, a third - also two-pass)
-    want = "scattered" if shuffle and probe["overflow"] <= pos.shape[0] // 5 else "two-pass"
+    # (the late list holds a quarter of the particles at float32: beyond four fifths of that estimated - this set, a third -
+    # also two-pass)
+    limit = dev.scatter_overflow_limit(pos.dtype, pos.shape[0])
+    assert limit <= pos.shape[0] // 5 < dev.scatter_late_capacity(pos.dtype, pos.shape[0])
+    want = "scattered" if shuffle and probe["overflow"] <= limit else "two-pass"
     assert st["path"] == want and st["attempts"] == 1
     host = pos.cpu().numpy().astype(np.float64)
     ref = omesh.paint(host, None, n, L, "cic")
@@ -757,9 +760,9 @@ def test_clustered_input_goes_to_the_two_pass_path_in_one_attempt(dev, shuffle):
         for na in (16, 8, 24, 4, 32, 2):
             mild = dev.synth_clustered_particles(n, n, L, seed=12, nattractors=na, shuffle=True, dtype=torch.float32)
             pm = dev.probe_input(mild, n, L)
-            if mild.shape[0] // 64 < pm["overflow"] <= mild.shape[0] // 5:
+            if mild.shape[0] // 64 < pm["overflow"] <= limit:
                 break
-        assert mild.shape[0] // 64 < pm["overflow"] <= mild.shape[0] // 5 and pm["groupable"] < 0.25, pm
+        assert mild.shape[0] // 64 < pm["overflow"] <= limit and pm["groupable"] < 0.25, pm
         stm = {}
         gm = dev.paint(mild, None, n, L, "cic", method="tiled", stats=stm)          # (check_dropped: nothing may be lost)
         assert stm["path"] == "scattered" and stm["attempts"] == 1 and stm["overflow"] > 0
