@@ -17,6 +17,10 @@ FFT_R2C, FFT_C2R, FFT_C2C_FWD, FFT_C2C_INV = 0, 1, 2, 3
 ERR_WORKSPACE = -4
 SUM_PARTS = 1024          # AST_SUM_PARTS
 BIN = {"integer": 0, "float64": 1}      # AST_BIN_*
+# AST_PAINT_* flag bits of ast_paint_tiled / ast_paint_tiled_stage, and the AST_PAINT_STAGE_* codes of the latter
+PAINT_TWO_PASS, PAINT_OVERWRITE, PAINT_DEFER_FOLD, PAINT_SCATTERED, PAINT_XSORTED = 1, 2, 4, 8, 16
+PAINT_STAGE_ALL, PAINT_STAGE_GROUP, PAINT_STAGE_WALK, PAINT_STAGE_FOLD = -1, 0, 1, 2
+PAINT_STAGE_GROUP_PART, PAINT_STAGE_RESET, PAINT_STAGE_LATE = 3, 4, 5
 
 
 class AstrildHipError(RuntimeError):

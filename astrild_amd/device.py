@@ -7,6 +7,8 @@ axis 0 slowest (``value_map[x, y, z]``, power_spectrum_3d.py:142-148), particle
 positions ``(Np, 3)`` like pmesh's ``paint`` (stats_subfind.py:125-131).
 """
 import ctypes as ct
+import itertools
+import os
 
 import numpy as np
 import torch
@@ -220,9 +222,7 @@ def probe_input(pos, nmesh, boxsize, shift=0.0, windows=256):
     ``groupable`` - the fraction of sampled runs of 32 consecutive particles the grouping kernel could turn into group records
     (:func:`sample_is_unordered`; < 0.25: no spatial order in memory) -, ``overflow`` - the estimated number of particles beyond
     the single pass's fixed tile segments (ast_paint_occupancy_probe: a sample of >= 8 particles per 8 x 8 x 32-cell tile) -
-    and ``max_tile`` - the largest estimated tile occupancy.  Evolved snapshots and halo catalogues
-    (stats_subfind.py:125-131) are clustered: their dense tiles overflow the segments, and the paint belongs on the exact
-    two-pass variant from the start."""
+    and ``max_tile`` - the largest estimated tile occupancy.  What ``paint`` makes of them: :func:`first_paint_path`."""
     L = _lib.lib()
     n, npart = int(nmesh), int(pos.shape[0])
     cbytes = int(L.ast_paint_occupancy_probe_bytes(n))
@@ -273,8 +273,7 @@ def auto_paint_method(npart, n, nx, window, hint=None, accumulate=False):
     "direct".  Above that, catalogues too small for the input probe (< 2^20 objects), or still sparse (< 64 per tile:
     halo catalogues, stats_subfind.py:125-131, clumpy by nature), take the exact two-pass lists - as fast as the single
     pass there and without its per-tile capacity (512^3, 32 per tile, TSC float64: direct 2.7 ms, tiled2 1.45; a clumpy
-    256^3 set at 64 per tile: single pass 1.0 ms through its overflow list, tiled2 0.2).  Dense input goes to "tiled",
-    where the probe picks single pass / scatter levels / two-pass from the input itself."""
+    256^3 set at 64 per tile: single pass 1.0 ms through its overflow list, tiled2 0.2).  Dense input goes to "tiled"."""
     per_tile = npart * 2048 / max(1, nx * n * n)
     if accumulate:                                   # (adding onto a grid: index lists + atomic tile flush; the round-1 threshold)
         return "tiled" if n % 32 == 0 and npart >= 65536 and per_tile >= 64 else "direct"
@@ -285,6 +284,102 @@ def auto_paint_method(npart, n, nx, window, hint=None, accumulate=False):
     return "tiled"
 
 
+def paint_flags(path, accumulate=False, defer_fold=False, xsorted=False):
+    """The AST_PAINT_* word of a tiled paint on ``path`` ("single-pass", "scattered", "two-pass").  XSORTED (the "xsorted" hint)
+    lives on the overwriting single pass only: a repaint on another path drops it."""
+    assert path in ("single-pass", "two-pass") or (path == "scattered" and not accumulate), (path, accumulate)
+    flags = (0 if accumulate else _lib.PAINT_OVERWRITE) | (_lib.PAINT_DEFER_FOLD if defer_fold else 0)
+    if path == "single-pass":
+        return flags | (_lib.PAINT_XSORTED if xsorted and not accumulate else 0)
+    return flags | (_lib.PAINT_TWO_PASS if path == "two-pass" else _lib.PAINT_SCATTERED)
+
+
+def paint_probe_kind(method, accumulate, hint, whole, check_dropped, npart):
+    """The probe a tiled paint runs before its first attempt (the table in :func:`paint`): "input" (:func:`probe_input`),
+    "order" (:func:`sample_is_unordered` alone - only for callers that synchronise anyway) or None."""
+    if method == "tiled2" or accumulate or hint is not None or npart < (1 << 20):
+        return None
+    return "input" if whole else "order" if check_dropped else None
+
+
+def first_paint_path(method, accumulate, hint, whole, check_dropped, npart, probed=None, unordered=None, limit=None):
+    """The path of a tiled paint's first attempt (the table in :func:`paint`).  ``probed``: what ``probe_input`` returned,
+    ``unordered``: what ``sample_is_unordered`` returned (None: not run, :func:`paint_probe_kind`), ``limit``:
+    ``scatter_overflow_limit``.  A wrong guess costs time, never correctness.  No spatial order in memory (under a quarter of
+    the sampled runs groupable): the bucket scatter, clustered or not - the two-pass variant makes two global atomics per
+    particle on such input (1024^3 clustered + shuffled: 130 ms against 24); tiles that overflow their segments go through the
+    late list, reserved once per workgroup and chunk.  The list holds a quarter of the particles at float32, an eighth at
+    float64: beyond four fifths of that estimated (``limit``), and for clustered input in file order (estimate above
+    npart / 64), the exact two-pass variant at once - slow on unordered input, but without any capacity."""
+    if method == "tiled2" or hint == "clustered":
+        return "two-pass"
+    if accumulate or hint in ("xsorted", "ordered"):        # (accumulate: index lists + atomic tile flush, no other path)
+        return "single-pass"
+    if hint == "scattered":
+        return "scattered"
+    kind = paint_probe_kind(method, accumulate, hint, whole, check_dropped, npart)
+    if kind == "input" and probed is not None:
+        if probed["groupable"] < 0.25 and probed["overflow"] <= limit:
+            return "scattered"
+        if probed["overflow"] > npart // 64:
+            return "two-pass"
+    return "scattered" if kind == "order" and unordered else "single-pass"
+
+
+def next_paint_path(path, probed, whole, check_dropped, npart, overflow=None, dropped=None):
+    """The path to paint again on after an attempt on ``path``, or None when it stands.  ``probed``: ``probe_input`` gave a
+    result for this call; ``overflow`` (the list statistics') and ``dropped``: None when not fetched - ``paint`` reads the drop
+    count after a scattered paint of the whole grid that R1 lets stand, 8 bytes.
+    R1 (callers that synchronise anyway: ``check_dropped``): too much went through the overflow list.  Particles without spatial
+    order in memory overflow the default stray segments: paint again with the two-level bucket scatter.  If that still
+    overflows, the input is strongly CLUSTERED (tiles far above twice the mean occupancy): the exact two-pass variant has no
+    capacity limit.  A scattered paint of a call the probe informed - unordered AND clustered - keeps its late list: it is the
+    fastest path for such input, and the result is complete either way.
+    R2: nothing falls outside the whole periodic grid, so a dropped deposit of the bucket scatter is a record its late list had
+    no room for (more than the probe estimated, or a "scattered" hint) - never lost, never reported as outside the buffer: the
+    exact two-pass lists paint it again."""
+    if path == "two-pass":
+        return None
+    if overflow is not None and check_dropped and overflow > npart // 64 and not (probed and path == "scattered"):
+        return "scattered" if path == "single-pass" else "two-pass"
+    return "two-pass" if path == "scattered" and whole and dropped else None
+
+
+def _check_paint_tensors(pos, mass=None, out=None, cells=0):
+    assert pos.is_cuda and pos.dim() == 2 and pos.shape[1] == 3 and pos.is_contiguous()
+    for t, count in ((mass, pos.shape[0]), (out, cells)):
+        assert t is None or (t.is_cuda and t.dtype == pos.dtype and t.numel() == count and t.is_contiguous())
+
+
+def _max_abs(t, count):
+    """max |t| over the first ``count`` elements (ast_minmax, one 16-byte fetch); 1.0 for None, nothing or all zeros: the
+    paint's mass bound (what its fixed-point tiles are scaled by), the bispectrum's field amplitude."""
+    if t is None or not count:
+        return 1.0
+    lo_hi = torch.empty(2, dtype=torch.float64, device=t.device)
+    check(_lib.lib().ast_minmax(ptr(t), real_code(t), count, ptr(lo_hi), stream()), "ast_minmax")
+    return float(lo_hi.abs().max()) or 1.0
+
+
+def _offset_planes(offset_planes):          # (first buffer plane, count) that get the offset; default: all
+    return (0, -1) if offset_planes is None else (int(offset_planes[0]), int(offset_planes[1]))
+
+
+def _paint_in_chunks(chunk, pos, mass, n, boxsize, window, **kw):
+    """The tile lists hold 32-bit particle indices: more than 2^32 - 65 particles (2048^3 on the largest grid one GPU
+    holds) are painted in chunks - the first one as asked for, the others accumulated onto it through the same LDS tiles."""
+    if kw["defer_fold"]:
+        raise _lib.AstrildHipError("defer_fold is not available for a paint in chunks (more than 2^32 - 65 particles)")
+    if isinstance(kw["offset"], str):        # "mean" means the mean of ALL particles, not of the first chunk
+        if kw["offset"] != "mean":
+            raise ValueError(kw["offset"])
+        kw["offset"] = total_mass(mass, pos.shape[0]) * float(kw["scale"]) / float(n) ** 3
+    for a in range(0, pos.shape[0], chunk):
+        kw["out"] = paint(pos[a:a + chunk], None if mass is None else mass[a:a + chunk], n, boxsize, window, **kw)
+        kw.update(accumulate=True, offset=0.0, hint=None)
+    return kw["out"]
+
+
 def paint(pos, mass, nmesh, boxsize, window="cic", scale=1.0, out=None, method="auto",
           x_start=0, nx_alloc=None, check_dropped=True, accumulate=None, defer_fold=False, offset=0.0,
           hint=None, stats=None, shift=0.0, offset_planes=None):
@@ -293,7 +388,7 @@ def paint(pos, mass, nmesh, boxsize, window="cic", scale=1.0, out=None, method="
     pos: (Np, 3) CUDA tensor (float32/float64); mass: (Np,) or None.
     Returns the grid ``(nx_alloc, nmesh, nmesh)`` in pos.dtype.
     method: "direct" (global float atomics), "tiled" (LDS tiles, single pass over the
-    particles), "tiled2" (LDS tiles, exact two-pass counting) or "auto" (= tiled when possible).
+    particles), "tiled2" (LDS tiles, exact two-pass counting) or "auto" (:func:`auto_paint_method`).
     accumulate: add into ``out`` (default when ``out`` is given) or overwrite it (default
     for a fresh grid; the tiled path then needs no zero-fill and flushes without atomics).
     defer_fold: (tiled overwrite of the whole grid only) skip the paint's last kernel and return
@@ -301,51 +396,42 @@ def paint(pos, mass, nmesh, boxsize, window="cic", scale=1.0, out=None, method="
     offset: (tiled overwrite only) owned cells are stored as ``sum - offset``, subtracted in double
     before the one rounding to the grid dtype; ``offset="mean"`` uses total mass * scale / nmesh^3,
     i.e. the grid holds rho - mean (only the DC mode changes, which FFTPower discards).
-    hint: "scattered" sizes the tiled overwrite paint's workspace for particles without spatial order in memory
-    (AST_PAINT_SCATTERED); "clustered" goes to the exact two-pass variant (no capacity limit per tile); "ordered" the
-    plain single pass.  Without a hint a paint of >= 2^20 particles onto the whole grid looks at the input first
-    (:func:`probe_input`: order in memory, tile occupancy tail) and picks single pass / scattered (no order in memory,
-    clustered or not) / two-pass (ordered and clustered) up front - also when ``check_dropped`` is False - instead of
-    finding out from the overflow list of a wasted attempt;
-    "xsorted" says they come in ascending x (lattice order, slab-ordered files): grouping and
-    column walk then overlap chunk by chunk (AST_PAINT_XSORTED; a wrong hint costs time, never correctness).  stats: a dict that receives the list statistics of the tiled overwrite paint.
+    hint: what the caller knows of the particles' order in memory (below; a wrong hint costs time, never correctness).
+    stats: a dict that receives the list statistics of the tiled overwrite paint, ``path`` and ``attempts``.
     shift: added to every coordinate in grid units (0.5 paints the second mesh of an interlaced pair).
     offset_planes: (first, count) of the buffer planes the offset applies to (default: all) - a slab buffer's
     ghost planes are added onto other ranks' cells and must stay plain sums.
+
+    Paths of a tiled paint: "single-pass" (fixed tile segments, an overflow list for the rest), "scattered"
+    (AST_PAINT_SCATTERED: bucket scatter of particles without spatial order in memory, a late list for what the segments
+    cannot hold), "two-pass" (AST_PAINT_TWO_PASS: exact index lists, no capacity).  The first attempt's
+    (:func:`first_paint_path`), first match, with whole = ``nx_alloc == nmesh and x_start == 0``:
+      method "tiled2", or hint "clustered" with "auto" / "tiled"   two-pass
+      accumulate                                                   single-pass; no list statistics, no repaint
+      hint "scattered" / "ordered"                                 scattered / single-pass
+      hint "xsorted" (ascending x: lattice order, slab files)      single-pass, grouping and walk overlapped chunk by chunk
+      no hint, >= 2^20 particles, whole (any check_dropped)        probe_input: None -> single-pass; groupable < 0.25 and
+                                                                   overflow <= scatter_overflow_limit -> scattered; else
+                                                                   overflow > Np // 64 -> two-pass; else single-pass
+      no hint, >= 2^20 particles, not whole, check_dropped         sample_is_unordered -> scattered, else single-pass
+      otherwise                                                    single-pass
+    Repaints after an attempt (overflow list too long, late list full): :func:`next_paint_path`.
     """
     L = _lib.lib()
     n = int(nmesh)
     nx = n if nx_alloc is None else int(nx_alloc)
-    assert pos.is_cuda and pos.dim() == 2 and pos.shape[1] == 3 and pos.is_contiguous()
+    _check_paint_tensors(pos, mass)
     code = real_code(pos)
-    if mass is not None:
-        assert mass.is_cuda and mass.dtype == pos.dtype and mass.numel() == pos.shape[0] and mass.is_contiguous()
     if accumulate is None:
         accumulate = out is not None
-    # The tile lists hold 32-bit particle indices: more than 2^32 - 65 particles (2048^3 on the largest grid one GPU holds)
-    # are painted in chunks - the first one as asked for, the others accumulated onto it through the same LDS tiles.
-    # ASTRILD_PAINT_CHUNK (particles) forces chunking at smaller sizes (tests).
-    import os
-    chunk = int(os.environ.get("ASTRILD_PAINT_CHUNK", 0)) or (2 ** 31 if pos.shape[0] >= 2 ** 32 - 65 else 0)
-    if chunk and pos.shape[0] > chunk and method != "direct" and _lib.WIN[window.lower()] != 0:
-        if defer_fold:
-            raise _lib.AstrildHipError("defer_fold is not available for a paint in chunks (more than 2^32 - 65 particles)")
-        if isinstance(offset, str):              # "mean" means the mean of ALL particles, not of the first chunk
-            if offset != "mean":
-                raise ValueError(offset)
-            offset = total_mass(mass, pos.shape[0]) * float(scale) / float(n) ** 3
-        for a in range(0, pos.shape[0], chunk):
-            part = paint(pos[a:a + chunk], None if mass is None else mass[a:a + chunk], n, boxsize, window, scale=scale, out=out,
-                         method=method, x_start=x_start, nx_alloc=nx_alloc, check_dropped=check_dropped,
-                         accumulate=accumulate if a == 0 else True, offset=offset if a == 0 else 0.0, hint=hint if a == 0 else None,
-                         shift=shift, offset_planes=offset_planes)
-            out = part
-        return out
     win = _lib.WIN[window.lower()]
     npart = pos.shape[0]
-    dropped = torch.zeros(1, dtype=torch.int64, device=pos.device)
-    ws_bytes = 0
-    # TWO_PASS | OVERWRITE | DEFER_FOLD | SCATTERED | XSORTED
+    # ASTRILD_PAINT_CHUNK (particles) forces chunking at smaller sizes (tests).
+    chunk = int(os.environ.get("ASTRILD_PAINT_CHUNK", 0)) or (2 ** 31 if npart >= 2 ** 32 - 65 else 0)
+    if chunk and npart > chunk and method != "direct" and win != 0:
+        return _paint_in_chunks(chunk, pos, mass, n, boxsize, window, scale=scale, out=out, method=method, x_start=x_start,
+                                nx_alloc=nx_alloc, check_dropped=check_dropped, accumulate=accumulate, defer_fold=defer_fold,
+                                offset=offset, hint=hint, shift=shift, offset_planes=offset_planes)
     if hint not in (None, "scattered", "xsorted", "clustered", "ordered"):
         raise ValueError(hint)
     if hint == "clustered" and method in ("auto", "tiled"):
@@ -353,23 +439,18 @@ def paint(pos, mass, nmesh, boxsize, window="cic", scale=1.0, out=None, method="
     was_auto = method == "auto"
     if was_auto and win != 0:
         method = auto_paint_method(npart, n, nx, window, hint, accumulate)
-    tflags = (1 if method == "tiled2" else 0) | (0 if accumulate else 2) | (4 if defer_fold else 0) | \
-             (8 if hint == "scattered" and not accumulate and method != "tiled2" else 0) | \
-             (16 if hint == "xsorted" and not accumulate and method != "tiled2" else 0)
-    if method in ("auto", "tiled", "tiled2") and win != 0 and npart < 2**32 - 65:
-        ws_bytes = int(L.ast_paint_tiled_workspace_bytes(win, code, npart, n, nx, tflags))
-    if method in ("tiled", "tiled2") and ws_bytes == 0:
-        if not was_auto:
-            raise _lib.AstrildHipError("tiled paint needs a CIC/TSC window and nmesh a multiple of 32")
-        method, tflags = "direct", 0                  # a buffer geometry the tiles do not cover
-    use_tiled = ws_bytes > 0 and method in ("tiled", "tiled2")      # ("auto" was resolved above: auto_paint_method)
-    if defer_fold and not (use_tiled and not accumulate and x_start == 0 and nx == n):
+    # (no workspace at any flags: a buffer geometry the tiles do not cover)
+    use_tiled = method in ("tiled", "tiled2") and win != 0 and npart < 2**32 - 65 and \
+        int(L.ast_paint_tiled_workspace_bytes(win, code, npart, n, nx, paint_flags("single-pass", accumulate))) > 0
+    if method in ("tiled", "tiled2") and not use_tiled and not was_auto:
+        raise _lib.AstrildHipError("tiled paint needs a CIC/TSC window and nmesh a multiple of 32")
+    whole = nx == n and int(x_start) == 0
+    if defer_fold and not (use_tiled and not accumulate and whole):
         raise _lib.AstrildHipError("defer_fold needs the tiled overwrite paint of the whole periodic grid")
     if out is None:
-        alloc = torch.empty if (use_tiled and not accumulate) else torch.zeros
-        out = alloc((nx, n, n), dtype=pos.dtype, device=pos.device)
+        out = (torch.empty if use_tiled and not accumulate else torch.zeros)((nx, n, n), dtype=pos.dtype, device=pos.device)
     else:
-        assert out.is_cuda and out.dtype == pos.dtype and out.numel() == nx * n * n and out.is_contiguous()
+        _check_paint_tensors(pos, None, out, nx * n * n)
         if not accumulate and not use_tiled:
             out.zero_()
     if offset != 0.0 and not (use_tiled and not accumulate):
@@ -378,80 +459,43 @@ def paint(pos, mass, nmesh, boxsize, window="cic", scale=1.0, out=None, method="
         if offset != "mean":
             raise ValueError(offset)
         offset = total_mass(mass, npart) * float(scale) / float(n) ** 3
-    off_planes = (0, -1) if offset_planes is None else offset_planes      # (first buffer plane, count) that get the offset
-    compact = use_tiled and not accumulate and method != "tiled2"       # single pass + overwrite: group / stray lists
-    attempts, probed, nd = 0, None, None
-    whole = nx == n and int(x_start) == 0
-    if compact and hint is None and npart >= (1 << 20) and whole:
-        probed = probe_input(pos, n, boxsize, shift)                    # (a wrong guess costs time, never correctness)
-        if probed is not None and probed["groupable"] < 0.25 and probed["overflow"] <= scatter_overflow_limit(pos.dtype, npart):
-            # no spatial order in memory: the bucket scatter, clustered or not - the two-pass variant makes two global
-            # atomics per particle on such input (1024^3 clustered + shuffled: 130 ms against 24); tiles that overflow
-            # their segments go through the late list, reserved once per workgroup and chunk (the list holds a quarter of
-            # the particles at float32, an eighth at float64: beyond four fifths of that estimated, the two-pass variant
-            # below, slow but without any capacity)
-            tflags |= 8
-        elif probed is not None and probed["overflow"] > npart // 64:
-            tflags = (tflags & ~(8 | 16)) | 1                           # clustered, in file order: the exact two-pass variant at once
-            compact = False
-        ws_bytes = int(L.ast_paint_tiled_workspace_bytes(win, code, npart, n, nx, tflags))
-    elif compact and hint is None and check_dropped and npart >= (1 << 20) and sample_is_unordered(pos, n, boxsize, shift):
-        tflags |= 8                                                     # (slab buffers: the order probe alone)
-        ws_bytes = int(L.ast_paint_tiled_workspace_bytes(win, code, npart, n, nx, tflags))
+    dropped, nd = torch.zeros(1, dtype=torch.int64, device=pos.device), None
     if use_tiled:
-        mass_bound = 1.0
-        if mass is not None and not accumulate and npart:
-            lo_hi = torch.empty(2, dtype=torch.float64, device=pos.device)      # bound for the fixed-point tiles
-            check(L.ast_minmax(ptr(mass), code, npart, ptr(lo_hi), stream()), "ast_minmax")
-            mass_bound = float(lo_hi.abs().max()) or 1.0
+        choice = (method, accumulate, hint, whole, check_dropped, npart)
+        kind = paint_probe_kind(*choice)
+        probed = probe_input(pos, n, boxsize, shift) if kind == "input" else None
+        unordered = sample_is_unordered(pos, n, boxsize, shift) if kind == "order" else None
+        path = first_paint_path(*choice, probed, unordered, scatter_overflow_limit(pos.dtype, npart) if probed else None)
+        mass_bound, attempts = 1.0 if accumulate else _max_abs(mass, npart), 0
         while True:
             attempts += 1
+            flags = paint_flags(path, accumulate, defer_fold, hint == "xsorted")
+            ws_bytes = int(L.ast_paint_tiled_workspace_bytes(win, code, npart, n, nx, flags))
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=pos.device)
             check(L.ast_paint_tiled(win, code, ptr(pos), ptr(mass), npart, n, float(boxsize), float(scale),
-                                    int(x_start), nx, ptr(out), ptr(ws), ws_bytes, ptr(dropped), tflags,
-                                    mass_bound, float(offset), int(off_planes[0]), int(off_planes[1]), float(shift), stream()),
+                                    int(x_start), nx, ptr(out), ptr(ws), ws_bytes, ptr(dropped), flags,
+                                    mass_bound, float(offset), *_offset_planes(offset_planes), float(shift), stream()),
                   "ast_paint_tiled")
-            st = None
-            if compact and (stats is not None or check_dropped):
+            st, nd = None, None
+            if not accumulate and path != "two-pass" and (stats is not None or check_dropped):     # group / stray lists exist
                 st = torch.empty(4, dtype=torch.int64, device=pos.device)
-                check(L.ast_paint_tiled_list_stats(ptr(ws), win, code, npart, n, nx, tflags, ptr(st), stream()),
+                check(L.ast_paint_tiled_list_stats(ptr(ws), win, code, npart, n, nx, flags, ptr(st), stream()),
                       "ast_paint_tiled_list_stats")
                 st = dict(zip(("groups", "strays", "overflow", "max_strays_per_tile"), st.cpu().tolist()))
-            # Too much went through the overflow list.  Particles without spatial order in memory overflow the
-            # default stray segments: paint again with the two-level bucket scatter (AST_PAINT_SCATTERED).  If that
-            # still overflows, the input is strongly CLUSTERED (tiles far above twice the mean occupancy): the exact
-            # two-pass variant has no capacity limit.  (Callers that synchronise anyway.)
-            if st is not None and check_dropped and st["overflow"] > npart // 64 and not (probed is not None and tflags & 8):
-                # (a scattered paint the probe chose knowingly - unordered AND clustered - keeps its late list: it is the
-                # fastest path for such input, and the result is complete either way)
-                dropped.zero_()
-                del ws
-                if not tflags & 8:
-                    tflags = (tflags | 8) & ~16
-                elif not tflags & 1:
-                    tflags = (tflags & ~8) | 1
-                    compact = False
-                ws_bytes = int(L.ast_paint_tiled_workspace_bytes(win, code, npart, n, nx, tflags))
-                continue
-            if tflags & 8 and whole:
-                # nothing falls outside the whole periodic grid: a dropped deposit of the bucket scatter is a record its
-                # late list had no room for (more than the probe estimated, or a "scattered" hint) - never lost, never
-                # reported as outside the buffer: the exact two-pass lists paint it again (one 8-byte read)
-                nd = int(dropped.item())
-                if nd:
-                    dropped.zero_()
-                    nd = None
-                    del ws
-                    tflags = (tflags & ~8) | 1
-                    compact = False
-                    ws_bytes = int(L.ast_paint_tiled_workspace_bytes(win, code, npart, n, nx, tflags))
-                    continue
-            if stats is not None:
-                stats.update(st or {}, scattered=bool(tflags & 8), attempts=attempts,
-                             path="two-pass" if tflags & 1 else "scattered" if tflags & 8 else "single-pass")
-                if probed is not None:
-                    stats["probe"] = probed
-            break
+            after = (path, probed is not None, whole, check_dropped, npart, st["overflow"] if st else None)
+            again = next_paint_path(*after)
+            if again is None and path == "scattered" and whole:
+                nd = int(dropped.item())                                # (a zero is reused by the check below)
+                again = next_paint_path(*after, nd)
+            if again is None:
+                break
+            dropped.zero_()
+            del ws                                # released BEFORE the next attempt's is allocated (peak memory at 1024^3)
+            path = again
+        if stats is not None:
+            stats.update(st or {}, scattered=path == "scattered", attempts=attempts, path=path)
+            if probed is not None:
+                stats["probe"] = probed
     else:
         check(L.ast_paint(win, code, ptr(pos), ptr(mass), npart, n, float(boxsize), float(scale),
                           int(x_start), nx, ptr(out), ptr(dropped), float(shift), stream()), "ast_paint")
@@ -459,11 +503,10 @@ def paint(pos, mass, nmesh, boxsize, window="cic", scale=1.0, out=None, method="
         if nd is None:
             nd = int(dropped.item())
         if nd:
-            raise _lib.AstrildHipError(f"{nd} deposits fell outside the grid buffer "
-                                       f"(x_start={x_start}, nx_alloc={nx})")
+            raise _lib.AstrildHipError(f"{nd} deposits fell outside the grid buffer (x_start={x_start}, nx_alloc={nx})")
     if defer_fold:
         rec = ct.c_void_p()
-        check(L.ast_paint_tiled_halo(ptr(ws), win, code, npart, n, nx, tflags, ct.byref(rec)), "ast_paint_tiled_halo")
+        check(L.ast_paint_tiled_halo(ptr(ws), win, code, npart, n, nx, flags, ct.byref(rec)), "ast_paint_tiled_halo")
         return out, PaintHalo(ws, rec, win)
     return out
 
@@ -482,29 +525,23 @@ class StagedPaint:
         L = _lib.lib()
         self.n = int(nmesh)
         self.nx = self.n if nx_alloc is None else int(nx_alloc)
-        assert pos.is_cuda and pos.dim() == 2 and pos.shape[1] == 3 and pos.is_contiguous()
-        assert out.is_cuda and out.dtype == pos.dtype and out.numel() == self.nx * self.n * self.n and out.is_contiguous()
+        _check_paint_tensors(pos, mass, out, self.nx * self.n * self.n)
         if hint not in (None, "scattered"):
             raise ValueError(hint)
         self.pos, self.mass, self.out = pos, mass, out
         self.code = real_code(pos)
         self.win = _lib.WIN[window.lower()]
         self.window = window.lower()
-        self.flags = 2 | (8 if hint == "scattered" else 0)                  # OVERWRITE [| SCATTERED]
+        self.flags = paint_flags("scattered" if hint == "scattered" else "single-pass")
         self.npart = pos.shape[0]
         self.ws_bytes = int(L.ast_paint_tiled_workspace_bytes(self.win, self.code, self.npart, self.n, self.nx, self.flags))
         if self.ws_bytes == 0 or self.win == 0 or self.npart >= 2**32 - 65:
             raise _lib.AstrildHipError("staged paint needs a CIC/TSC window and nmesh a multiple of 32")
         self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=pos.device)
         self.dropped = torch.zeros(1, dtype=torch.int64, device=pos.device)
-        self.mass_bound = 1.0
-        if mass is not None and self.npart:
-            lo_hi = torch.empty(2, dtype=torch.float64, device=pos.device)
-            check(L.ast_minmax(ptr(mass), self.code, self.npart, ptr(lo_hi), stream()), "ast_minmax")
-            self.mass_bound = float(lo_hi.abs().max()) or 1.0
-        off = (0, -1) if offset_planes is None else offset_planes
+        self.mass_bound = _max_abs(mass, self.npart)
         self.args = (float(boxsize), float(scale), int(x_start), self.nx)
-        self.tail = (self.mass_bound, float(offset), int(off[0]), int(off[1]), float(shift))
+        self.tail = (self.mass_bound, float(offset), *_offset_planes(offset_planes), float(shift))
         self.row_planes = int(L.ast_paint_tile_row_planes())
         self.nrows_total = int(L.ast_paint_tile_rows(self.nx))
         self.periodic = self.nx == self.n and int(x_start) == 0
@@ -526,38 +563,32 @@ class StagedPaint:
 
     def group(self):
         self.dropped.zero_()
-        self._stage(0, 0, 0)
+        self._stage(_lib.PAINT_STAGE_GROUP, 0, 0)
 
     def reset(self):
         """Instead of group(), before the first group_part()."""
         self.dropped.zero_()
-        self._stage(4, 0, 0)
+        self._stage(_lib.PAINT_STAGE_RESET, 0, 0)
 
     def group_part(self, k, parts, closed_row0=0, closed_nrows=0, span=1):
         """The lists of parts k .. k + span - 1 of `parts` equal parts of the particle array, in one launch (x-ordered input,
         slab buffers).  closed_*: the tile rows walked so far, one range modulo the buffer's rows; a particle that turns up
         for one of them is counted as dropped (check() raises): the order that was promised did not hold."""
         assert 1 <= parts <= 65535 and span >= 1 and 0 <= k and k + span <= parts
-        self._stage(3, k, parts | ((span - 1) << 16), closed_row0, closed_nrows)
+        self._stage(_lib.PAINT_STAGE_GROUP_PART, k, parts | ((span - 1) << 16), closed_row0, closed_nrows)
 
     def walk(self, row0, nrows):
-        self._stage(1, row0, nrows)
+        self._stage(_lib.PAINT_STAGE_WALK, row0, nrows)
 
     def fold(self, row0, nrows):
         """FOLD of the tile rows [row0, row0 + nrows).  After :meth:`defer_folds` only the rows named there get their records
         added here; the others get their overflow-list deposits only (AST_PAINT_STAGE_LATE) and their records when the
         consumer's z pass loads the planes (:meth:`halo_args`)."""
         if self._explicit_rows is None:
-            self._stage(2, row0, nrows)
+            self._stage(_lib.PAINT_STAGE_FOLD, row0, nrows)
             return
-        r = row0
-        while r < row0 + nrows:
-            kind = r in self._explicit_rows
-            e = r
-            while e < row0 + nrows and (e in self._explicit_rows) == kind:
-                e += 1
-            self._stage(2 if kind else 5, r, e - r)
-            r = e
+        for explicit, run in itertools.groupby(range(row0, row0 + nrows), key=self._explicit_rows.__contains__):
+            self._stage(_lib.PAINT_STAGE_FOLD if explicit else _lib.PAINT_STAGE_LATE, next(run), 1 + len(list(run)))
 
     _explicit_rows = None
 
@@ -1088,13 +1119,9 @@ def bispectrum(field, boxsize, edges, triangles):
     # The triangle sums form f_i f_j f_l of fp32 fields in fp32 (only the running sums are double): a field in physical units
     # (a mass-weighted grid in Msun/h per cell) would overflow the product above |D| ~ 7e12.  The shell fields are therefore
     # built from the spectrum divided by A = max |field| - values of order one - and the sums multiplied back by A^3.
-    amp = 1.0
-    if field.dtype == torch.float32 and field.numel():
-        lo_hi = torch.empty(2, dtype=torch.float64, device=field.device)
-        check(_lib.lib().ast_minmax(ptr(field), real_code(field), field.numel(), ptr(lo_hi), stream()), "ast_minmax")
-        amp = float(lo_hi.abs().max()) or 1.0
-        if not np.isfinite(amp):
-            raise _lib.AstrildHipError("bispectrum: the field holds inf / NaN")
+    amp = _max_abs(field, field.numel()) if field.dtype == torch.float32 else 1.0
+    if not np.isfinite(amp):
+        raise _lib.AstrildHipError("bispectrum: the field holds inf / NaN")
     # FUSED tail (default where it applies: fp32 tile sizes, <= 32 shells): every shell's masked x and y passes into its OWN
     # scratch spectrum, then ONE kernel that runs the z passes of all shells row by row and forms the triangle sums from
     # LDS (ast_fft_tile_c2r_triangles) - the 31 real cubes (0.5 GB each at 512^3, written once and read back once) never

@@ -41,6 +41,20 @@ def test_ctypes_table_matches_header():
     assert lib.ast_version() >= 100       # host-only call, no GPU needed
 
 
+def test_paint_flag_and_stage_constants_match_header():
+    """The AST_PAINT_* flag bits and AST_PAINT_STAGE_* codes of the header, under the same names without the prefix in _lib."""
+    from astrild_amd import _lib
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    defines = {name: int(value) for name, value in re.findall(r"^#define\s+AST_(PAINT_[A-Z_]+)\s+\(?(-?\d+)\)?\s*$", src, flags=re.M)}
+    assert sorted(defines) == sorted(["PAINT_TWO_PASS", "PAINT_OVERWRITE", "PAINT_DEFER_FOLD", "PAINT_SCATTERED", "PAINT_XSORTED",
+                                      "PAINT_STAGE_ALL", "PAINT_STAGE_GROUP", "PAINT_STAGE_WALK", "PAINT_STAGE_FOLD",
+                                      "PAINT_STAGE_GROUP_PART", "PAINT_STAGE_RESET", "PAINT_STAGE_LATE"])
+    for name, value in defines.items():
+        assert getattr(_lib, name) == value, name
+    assert sorted(n for n in vars(_lib) if n.startswith("PAINT_")) == sorted(defines)
+    assert defines["PAINT_STAGE_ALL"] == -1 and defines["PAINT_XSORTED"] == 16
+
+
 def test_product_never_imports_the_oracle():
     pkg = os.path.join(ROOT, "astrild_amd")
     for dirpath, _, files in os.walk(pkg):
