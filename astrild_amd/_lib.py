@@ -164,6 +164,9 @@ SIGNATURES = {
     "ast_profile2d_band_rows": (_i, []),
     "ast_profile2d_workspace_bytes": (_sz, [_sz, _sz, _i]),
     "ast_profile2d": (_i, [_vp, _i, _sz, _sz, _sz, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
+    "ast_tunnels_workspace_bytes": (_sz, [_sz, _i]),
+    "ast_tunnels_max_npix": (_i, []),
+    "ast_tunnels_find": (_i, [_vp, _vp, _sz, _i, _i, _vp, _sz, _vp, _vp, _vp]),
 }
 
 _lib = None

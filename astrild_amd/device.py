@@ -1334,3 +1334,89 @@ def annulus_profiles(skymap, x_pix, y_pix, rad_pix, extend, nbins, delta_eta=Non
                             band_rows, ptr(starts), n_work, ptr(work), ws_bytes, ptr(sums), ptr(counts), stream()),
           "ast_profile2d")
     return sums, counts
+
+
+# ------------------------------------------------------------------ tunnels void finder
+def check_tunnels_tracers(x_pix, y_pix, npix):
+    """The argument checks of ``tunnels_voids``, before any GPU work: ``(x, y, npix, on_device)`` with x, y 1D integer
+    arrays (numpy, or device tensors when they came as tensors) or ValueError."""
+    npix = int(npix)
+    if npix < 1:
+        raise ValueError(f"npix must be positive, got {npix}")
+    on_device = isinstance(x_pix, torch.Tensor) and isinstance(y_pix, torch.Tensor)
+    if on_device:
+        x, y = x_pix.reshape(-1), y_pix.reshape(-1)
+        integer = not (x.dtype.is_floating_point or x.dtype.is_complex or y.dtype.is_floating_point
+                       or y.dtype.is_complex or x.dtype == torch.bool or y.dtype == torch.bool)
+    else:
+        x, y = np.asarray(x_pix).reshape(-1), np.asarray(y_pix).reshape(-1)
+        integer = (x.dtype.kind in "iu" and y.dtype.kind in "iu") or (x.size == 0 and y.size == 0)
+    if not integer:
+        raise ValueError(f"tracer coordinates must be integer pixel indices, got {x.dtype} and {y.dtype}")
+    n = int(x.shape[0])
+    if int(y.shape[0]) != n:
+        raise ValueError(f"x_pix and y_pix must have one entry per tracer, got {n} and {int(y.shape[0])}")
+    if n >= 1 << 31:
+        raise ValueError(f"{n} tracers: fewer than 2^31 are supported")
+    if n:
+        lo, hi = min(int(x.min()), int(y.min())), max(int(x.max()), int(y.max()))
+        if lo < 0 or hi >= npix:
+            raise ValueError(f"tracer coordinates must lie in [0, {npix}), got {lo} .. {hi}")
+        key = (y.to(torch.int64) if on_device else y.astype(np.int64)) * npix + x
+        distinct = int(torch.unique(key).numel()) if on_device else len(np.unique(key))
+        if distinct != n:
+            raise ValueError(f"{n - distinct} duplicate tracers: all tracers must be distinct")
+    if not on_device:
+        x, y = x.astype(np.int32), y.astype(np.int32)
+    return x, y, npix, on_device
+
+
+def tunnels_voids(x_pix, y_pix, npix, return_violations=False):
+    """The tunnels voids of tracers on an ``npix``^2 map (rays/voids/tunnel.py; ``ast_tunnels_find``): the circles
+    through at least three tracers with no tracer strictly inside and their centre in the map, as an (M, 7) int64 array
+    of records (i, e, k, n_on, X, Y, W) sorted by (i, e, k): i the smallest tracer index on the circle, e the tracer on
+    it with all others strictly left of i -> e, k the next one counter-clockwise, n_on the number of tracers on it,
+    centre (X / W, Y / W) (``tunnels_circles`` forms the floats).  ``x_pix`` (column) / ``y_pix`` (row): distinct integer
+    pixel coordinates in [0, npix), npix <= ``ast_tunnels_max_npix()``; numpy arrays give a numpy array, device tensors
+    a device tensor.  ValueError before any GPU work otherwise.  Fewer than three tracers, or only collinear ones,
+    give an empty array.  All decisions are exact integers, so repeated calls are bit-identical.  The device also counts
+    violations (circles it found with a tracer inside, walks that did not end): any raises AstrildHipError, unless
+    ``return_violations`` asks for ``(records, violations)`` instead.
+    ASTRILD_TUNNELS_CELLS=0 forces a single cell (every scan sees all tracers) instead of the cell grid."""
+    x, y, npix, on_device = check_tunnels_tracers(x_pix, y_pix, npix)
+    lib = _lib.lib()
+    if npix > lib.ast_tunnels_max_npix():
+        raise ValueError(f"npix={npix}: at most {lib.ast_tunnels_max_npix()} (the in-circle test is exact in int64)")
+    n = int(x.shape[0])
+    if n < 3:
+        none = torch.zeros((0, 7), dtype=torch.int64, device=device()) if on_device else np.zeros((0, 7), np.int64)
+        return (none, 0) if return_violations else none
+    xd, yd = as_device(x, torch.int32), as_device(y, torch.int32)
+    single = os.environ.get("ASTRILD_TUNNELS_CELLS", "1") == "0"
+    ws_bytes = lib.ast_tunnels_workspace_bytes(n, npix)
+    work = torch.empty(ws_bytes, dtype=torch.uint8, device=xd.device)
+    records = torch.empty((2 * n, 7), dtype=torch.int64, device=xd.device)
+    count = torch.empty(2, dtype=torch.int64, device=xd.device)
+    check(lib.ast_tunnels_find(ptr(xd), ptr(yd), n, npix, int(single), ptr(work), ws_bytes, ptr(records), ptr(count),
+                               stream()), "ast_tunnels_find")
+    m, violations = (int(v) for v in count.cpu())
+    if (violations and not return_violations) or m > 2 * n:
+        raise _lib.AstrildHipError(f"ast_tunnels_find: {violations} violations (circles with a tracer inside or walks "
+                                   f"that did not end), {m} records for {n} tracers")
+    records = records[:m]
+    records = records[torch.argsort(records[:, 0] * (1 << 31) + records[:, 1])]     # (i, e) is unique per circle
+    records = records if on_device else to_numpy(records)
+    return (records, violations) if return_violations else records
+
+
+def tunnels_circles(records, x_pix, y_pix):
+    """``(cx, cy, r)`` in pixels, float64 numpy arrays, from the integer records of ``tunnels_voids``: cx = X / W,
+    cy = Y / W, r = hypot(X - W x_i, Y - W y_i) / W."""
+    rec = to_numpy(records) if isinstance(records, torch.Tensor) else np.asarray(records, dtype=np.int64)
+    rec = rec.reshape(-1, 7)
+    x = to_numpy(x_pix) if isinstance(x_pix, torch.Tensor) else np.asarray(x_pix)
+    y = to_numpy(y_pix) if isinstance(y_pix, torch.Tensor) else np.asarray(y_pix)
+    x, y = x.reshape(-1).astype(np.int64), y.reshape(-1).astype(np.int64)
+    X, Y, W = rec[:, 4], rec[:, 5], rec[:, 6]
+    ux, uy = X - W * x[rec[:, 0]], Y - W * y[rec[:, 0]]
+    return X / W, Y / W, np.hypot(ux, uy) / W

@@ -854,6 +854,28 @@ int ast_profile2d(const void* map_d, int dtype, size_t ny, size_t nx, size_t n_o
                   const long long* item_start_d, size_t n_work, void* work_d, size_t work_bytes, double* sums_d,
                   long long* counts_d, void* stream);
 
+/* ------------------------------------------------- tunnels void finder */
+
+/* The tunnels void finder of rays/voids/tunnel.py (TunnelsFinder.find_voids, :158-248; Cautun et al.,
+ * arXiv:1710.01730), which there is an external program: the circles through at least three tracers with no tracer
+ * strictly inside, i.e. the distinct circumcircles of the tracers' Delaunay triangles, whose centre lies in the map.
+ * x_d, y_d: int32 pixel coordinates (x the column, y the row), 0 <= x, y < npix <= ast_tunnels_max_npix() (16384:
+ * coordinate differences below 2^14 keep the in-circle determinant in int64), all distinct; the host checks this.
+ * Every decision is exact integer arithmetic.  records_d[2 n][7] int64 receives, in no particular order, one record
+ * (i, e, k, n_on, X, Y, W) per circle: i the smallest tracer index on it, e the tracer on it with every other one
+ * strictly left of i -> e, k the next one counter-clockwise after e as seen from i, n_on >= 3 the number of tracers
+ * on it, and the centre (X / W, Y / W) from the triple (i, e, k): b' = b - a, c' = c - a, D = b'x c'y - b'y c'x,
+ * Ux = c'y |b'|^2 - b'y |c'|^2, Uy = b'x |c'|^2 - c'x |b'|^2, X = 2 D ax + Ux, Y = 2 D ay + Uy, W = 2 D > 0; kept when
+ * 0 <= X, Y <= W (npix - 1).  count_d[0] = the number of records (never above 2 n), count_d[1] = violations: circles
+ * found with a tracer inside, or walks that did not end; it must be 0.  The set of records is the same on every
+ * call.  n < 3: no records.  single_cell != 0 puts all tracers into one cell, so that every scan sees all of them.
+ * Workspace: ast_tunnels_workspace_bytes(n, npix) bytes (0: npix outside 1..16384 or n >= 2^31).  Nothing is
+ * allocated and nothing synchronises. */
+size_t ast_tunnels_workspace_bytes(size_t n, int npix);
+int ast_tunnels_max_npix(void);
+int ast_tunnels_find(const int* x_d, const int* y_d, size_t n, int npix, int single_cell, void* work_d,
+                     size_t work_bytes, long long* records_d, unsigned long long* count_d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
