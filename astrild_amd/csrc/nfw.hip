@@ -67,8 +67,9 @@ nfw_paint_kernel(HaloSoA h, double extent, int dir_mask, int suppress, double su
     for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total;
          t += (long long)gridDim.x * blockDim.x) {
         const int i = i_lo + (int)(t / w), j = j_lo + (int)(t % w);
-        const double ex = (j == S - 1 ? stop : (double)j * step) - r200 * extent;        // thetax = edges[j]
-        const double ey = (i == S - 1 ? stop : (double)i * step) - r200 * extent;        // thetay = edges[i]
+        // np.linspace(0, stop, S): the last sample is `stop` itself - except for S == 1, whose only sample is 0
+        const double ex = (S > 1 && j == S - 1 ? stop : (double)j * step) - r200 * extent;   // thetax = edges[j]
+        const double ey = (S > 1 && i == S - 1 ? stop : (double)i * step) - r200 * extent;   // thetay = edges[i]
         const double rr = sqrt(ex * ex + ey * ey);
         const double f = nfw_f(rr / rs);
         double sup = 1.0;

@@ -99,7 +99,7 @@ extern "C" int ast_order_statistics(const void* buf, int dtype, size_t count, co
     AST_CHECK_ARG(dtype == AST_F32 || dtype == AST_F64);
     hipStream_t s = ast::as_stream(stream);
     const unsigned g = ast::stream_grid(count, 256);
-    static unsigned long long hist[2048];
+    unsigned long long hist[2048];                      // per call: host threads must not share it
     for (int j = 0; j < nk; ++j) {
         AST_CHECK_ARG(ks_host[j] < count);
         size_t k = ks_host[j];

@@ -374,10 +374,23 @@ def add(a, b, out=None):
 
 
 # --------------------------------------------------- f-2 NFW halo stamps
-def nfw_paint(halo_cat, extent, direction, suppress, suppression_R, npix, signal, out=None):
+def nfw_stamp_npix(halo_cat, extent, stamp_npix=None):
+    """Edge length [pixels] of every halo's stamp: ``int(2 * r200_pix * extent) + 1`` (sky_utils.py:112,130) unless the
+    caller states the sizes.  A size cannot be handed over as an r200_pix: ``(npix - 1) / (2 * extent)`` times
+    ``2 * extent`` may round to just below npix - 1, and int() then drops a pixel."""
+    if stamp_npix is not None:
+        stamp = np.asarray(stamp_npix, dtype=np.int64)
+        if stamp.shape != (len(halo_cat["m200"]),) or (stamp < 1).any():
+            raise ValueError("nfw_paint: stamp_npix holds one size >= 1 per halo")
+        return stamp
+    return np.array([int(2 * r * extent) + 1 for r in np.asarray(halo_cat["r200_pix"])], dtype=np.int64)
+
+
+def nfw_paint(halo_cat, extent, direction, suppress, suppression_R, npix, signal, out=None, stamp_npix=None):
     """Add the NFW deflection-angle ("alpha") or moving-lens temperature ("dT") stamp of
     every halo of ``halo_cat`` (dict of equal-length sequences with astrild's keys) onto an
-    npix x npix map — SkyUtils.analytic_Halo_signal_to_SkyArray (sky_utils.py:79-137)."""
+    npix x npix map — SkyUtils.analytic_Halo_signal_to_SkyArray (sky_utils.py:79-137).
+    stamp_npix: the stamps' edge lengths, where they are not to be derived from ``r200_pix``."""
     nh = len(halo_cat["m200"])
     f64 = lambda key: as_device(np.ascontiguousarray(np.asarray(halo_cat[key], dtype=np.float64)))
     i32 = lambda arr: as_device(np.ascontiguousarray(np.asarray(arr, dtype=np.int32)))
@@ -389,8 +402,7 @@ def nfw_paint(halo_cat, extent, direction, suppress, suppression_R, npix, signal
     mask = sum(1 << int(d) for d in set(int(d) for d in direction))
     if sig == 0 and int(np.sum(list(direction))) > 1:
         raise AssertionError("Only 0 and 1 are valid direction indications.")
-    r200_pix = np.asarray(halo_cat["r200_pix"])
-    stamp = np.array([int(2 * r * extent) + 1 for r in r200_pix])       # sky_utils.py:112,130
+    stamp = nfw_stamp_npix(halo_cat, extent, stamp_npix)
     dist = as_device(np.ascontiguousarray(np.asarray(halo_cat["Dc"], dtype=np.float64) * 0.6774))
     vx = f64("theta1_tv") if sig == 1 else None
     vy = f64("theta2_tv") if sig == 1 else None

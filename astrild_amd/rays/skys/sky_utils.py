@@ -58,9 +58,8 @@ class SkyUtils:
                       suppression_R, signal, vel=(0.0, 0.0)):
         # a stamp of npix pixels centred on itself: the map IS the stamp
         cat = {"r200_deg": [theta_200c], "m200": [M_200c], "c_NFW": [c_200c], "Dc": [angu_diam_dist / 0.6774],
-               "theta1_pix": [npix // 2], "theta2_pix": [npix // 2], "theta1_tv": [vel[0]], "theta2_tv": [vel[1]],
-               "r200_pix": [(npix - 1) / (2.0 * extent)]}
-        out = lensing.nfw_paint(cat, extent, direction, suppress, suppression_R, npix, signal)
+               "theta1_pix": [npix // 2], "theta2_pix": [npix // 2], "theta1_tv": [vel[0]], "theta2_tv": [vel[1]]}
+        out = lensing.nfw_paint(cat, extent, direction, suppress, suppression_R, npix, signal, stamp_npix=[npix])
         return to_numpy(out)
 
     @staticmethod

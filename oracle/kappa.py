@@ -278,13 +278,17 @@ def nfw_temperature_perturbation_map(theta_200c, m_200c, c_200c, vel, angu_diam_
 
 
 def add_patch_to_map(limg, simg, cen_pix):
-    """rays/skys/sky_utils.py:140-173: add a stamp, clipped at the map boundary."""
-    rad = int(len(simg) / 2)
-    xe = np.arange(cen_pix[0] - rad, cen_pix[0] + rad + 1)
-    ye = np.arange(cen_pix[1] - rad, cen_pix[1] + rad + 1)
-    xok = (0 <= xe) & (xe < len(limg))
-    yok = (0 <= ye) & (ye < len(limg))
-    limg[ye[yok].min(): ye[yok].max() + 1, xe[xok].min(): xe[xok].max() + 1] += simg[np.ix_(yok, xok)]
+    """rays/skys/sky_utils.py:140-173: add a stamp, clipped at the map boundary.  Stamp pixel (i, j) of an S x S stamp
+    lands on map pixel (cen_y - S // 2 + i, cen_x - S // 2 + j).  For an odd stamp that touches the map this is the
+    reference's sum, addition for addition.  Two extensions, where the reference raises (IndexError, ValueError): an
+    even stamp follows the same rule, and a stamp with no pixel on the map adds nothing."""
+    s, n = len(simg), len(limg)
+    x0, y0 = cen_pix[0] - s // 2, cen_pix[1] - s // 2
+    j_lo, j_hi = max(0, -x0), min(s, n - x0)
+    i_lo, i_hi = max(0, -y0), min(s, n - y0)
+    if j_hi <= j_lo or i_hi <= i_lo:
+        return limg
+    limg[y0 + i_lo: y0 + i_hi, x0 + j_lo: x0 + j_hi] += simg[i_lo:i_hi, j_lo:j_hi]
     return limg
 
 

@@ -248,3 +248,105 @@ def test_deflection_to_shear_known_answer():
     g1, g2 = ok.deflection_to_shear(a1, a2, h)
     npt.assert_allclose(g1, 0.5 * ((1 - (0.3 + 0.2 * j)) - (1 + 0.1)), rtol=0, atol=1e-12)
     npt.assert_allclose(g2, 0.5 * (-0.05 - 0.2 * i), rtol=0, atol=1e-12)
+
+
+def _add_patch_by_mask(limg, simg, cen_pix):
+    """The reference's add_patch_to_map step by step (rays/skys/sky_utils.py:159-172): pixel coordinates of an odd
+    stamp around its centre, the 2-D mask of those on the map, the surviving rows and columns from the mask's sums,
+    the stamp cut by the mask and added to the slice the survivors span."""
+    rad = int(len(simg) / 2)
+    xs = np.arange(cen_pix[0] - rad, cen_pix[0] + rad + 1)
+    ys = np.arange(cen_pix[1] - rad, cen_pix[1] + rad + 1)
+    px, py = np.meshgrid(xs, ys)
+    on_map = (0 <= px) & (px < len(limg)) & (0 <= py) & (py < len(limg))
+    cols, rows = on_map.sum(axis=0) > 0, on_map.sum(axis=1) > 0
+    cut = simg[on_map].reshape((rows.sum(), cols.sum()))
+    limg[int(ys[rows].min()): int(ys[rows].max()) + 1, int(xs[cols].min()): int(xs[cols].max()) + 1] += cut
+    return limg
+
+
+def test_add_patch_to_map_equals_the_reference_mask_code_for_odd_stamps_on_the_map():
+    rng = np.random.default_rng(3)
+    n = 12
+    base = rng.standard_normal((n, n))
+    checked = 0
+    for s in (1, 3, 5, 7, 11, 13, 25, 31):
+        stamp = rng.standard_normal((s, s))
+        for cx in range(-s // 2 - 2, n + s // 2 + 3):
+            for cy in range(-s // 2 - 2, n + s // 2 + 3):
+                touches = -(s // 2) <= cx < n + s // 2 and -(s // 2) <= cy < n + s // 2
+                got = ok.add_patch_to_map(base.copy(), stamp, (cx, cy))
+                if touches:
+                    assert np.array_equal(got, _add_patch_by_mask(base.copy(), stamp, (cx, cy))), (s, cx, cy)
+                    checked += 1
+                else:
+                    with pytest.raises(ValueError):          # the reference: min() of an empty selection
+                        _add_patch_by_mask(base.copy(), stamp, (cx, cy))
+                    assert np.array_equal(got, base), (s, cx, cy)
+    assert checked > 3000
+
+
+def test_add_patch_to_map_even_stamps_pixel_by_pixel():
+    """The extension: stamp pixel (i, j) -> map pixel (cen_y - S // 2 + i, cen_x - S // 2 + j), dropped off the map."""
+    rng = np.random.default_rng(4)
+    n = 9
+    base = rng.standard_normal((n, n))
+    for s in (2, 4, 6, 26):
+        stamp = rng.standard_normal((s, s))
+        with pytest.raises(IndexError):                      # the reference: S + 1 coordinates against S pixels
+            _add_patch_by_mask(base.copy(), stamp, (4, 4))
+        for cx in range(-s, n + s + 1):
+            for cy in range(-s, n + s + 1):
+                ref = base.copy()
+                for i in range(s):
+                    for j in range(s):
+                        y, x = cy - s // 2 + i, cx - s // 2 + j
+                        if 0 <= y < n and 0 <= x < n:
+                            ref[y, x] += stamp[i, j]
+                assert np.array_equal(ok.add_patch_to_map(base.copy(), stamp, (cx, cy)), ref), (s, cx, cy)
+
+
+def test_nfw_one_pixel_stamp_is_sampled_at_minus_r200_extent():
+    """np.linspace(0, stop, 1) is [0]: the only pixel of a one-pixel stamp sits at (-r200 extent, -r200 extent), where
+    the x and y deflections are negative."""
+    a = ok.nfw_deflection_angle_map(0.05, 7e13, 2.0, 700.0, npix=1, extent=3, direction=[0])
+    b = ok.nfw_deflection_angle_map(0.05, 7e13, 2.0, 700.0, npix=3, extent=3, direction=[0])
+    assert a.shape == (1, 1) and a[0, 0] < 0 and a[0, 0] == b[0, 0]
+
+
+def _peaks_by_double_loop(img, lo, hi):
+    a = np.asarray(img, dtype=np.float64)
+    vals, pos = [], []
+    for y in range(1, a.shape[0] - 1):
+        for x in range(1, a.shape[1] - 1):
+            c = a[y, x]
+            if all(c > a[y + dy, x + dx] for dy in (-1, 0, 1) for dx in (-1, 0, 1) if (dy, dx) != (0, 0)) \
+                    and lo <= c < hi:
+                vals.append(c)
+                pos.append((y, x))
+    return np.array(vals, dtype=np.float64), np.array(pos, dtype=np.int64).reshape(-1, 2)
+
+
+@pytest.mark.parametrize("npix", [3, 4, 5, 16, 17, 33])
+def test_locate_peaks_equals_a_double_loop_over_the_interior(npix):
+    rng = np.random.default_rng(npix)
+    maps = [rng.standard_normal((npix, npix)),
+            rng.integers(0, 3, (npix, npix)).astype(np.float64),             # ties everywhere
+            np.full((npix, npix), 2.0)]
+    special = rng.standard_normal((npix, npix))
+    special[rng.integers(0, npix, 3), rng.integers(0, npix, 3)] = np.nan
+    special[rng.integers(0, npix, 3), rng.integers(0, npix, 3)] = -np.inf
+    special[npix // 2, npix // 2] = np.inf
+    maps.append(special)
+    maps.append(rng.standard_normal((npix, npix)).astype(np.float32))
+    for img in maps:
+        heights = np.sort(_peaks_by_double_loop(img, -np.inf, np.inf)[0])
+        bounds = [(-np.inf, np.inf), (0.0, 1.0), (1.0, 0.0)]
+        if len(heights) >= 2 and np.isfinite(heights).all():
+            bounds.append((heights[0], heights[-1]))                         # >= lo kept, < hi dropped
+        for lo, hi in bounds:
+            with np.errstate(invalid="ignore"):
+                v, p = ok.locate_peaks(img, np.array([lo, hi]))
+            rv, rp = _peaks_by_double_loop(img, lo, hi)
+            assert np.array_equal(v, rv) and np.array_equal(p, rp), (npix, lo, hi)
+    assert len(ok.locate_peaks(maps[2], np.array([-np.inf, np.inf]))[0]) == 0
