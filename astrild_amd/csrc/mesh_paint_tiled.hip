@@ -30,6 +30,7 @@
 #include "ast_common.h"
 #include "paint_tile_geom.h"
 #include <algorithm>
+#include <climits>
 #include <cstdlib>
 #include <mutex>
 #include <type_traits>
@@ -878,7 +879,7 @@ late_deposit_kernel(const T* __restrict__ late_list, const unsigned long long* _
                     TileGeom g, double scale, T* __restrict__ grid, unsigned long long* dropped, int x_lo, int x_hi,
                     unsigned long long n_below = ~0ull) {
     const unsigned long long n = min(*late, late_cap);
-    if (n >= n_below) return;                         // a long list goes through LDS tiles (run_tiled, scattered branch)
+    if (n >= n_below) return;                         // a long list goes through LDS tiles (TiledPaint::scattered_path)
     for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
          i += (unsigned long long)gridDim.x * blockDim.x)
         deposit_record_global<T, W>(late_list[4 * i], late_list[4 * i + 1], late_list[4 * i + 2], late_list[4 * i + 3], g, scale,
@@ -1251,26 +1252,11 @@ column_deposit_kernel(const T* __restrict__ pos, const T* __restrict__ mass, Til
     // The z planes of the tile form a RING of LZ slots: local plane c of tile tz lives in slot
     // (c + tz * TZ) mod LZ, so the W-1 halo planes carried from one tile to the next stay where
     // they are and the flush only has to re-arm the TZ slots it stored.
-    // Row pitch PZ >= LZ cells (WALK_PZ, default LZ).  The walk is bound by its LDS atomics (rocprofv3: LDS 77 % busy, 59 %
-    // of its cycles bank conflicts: the 32 z-consecutive particles of a half wave fill all 64 banks, so every particle
-    // the jitter moved to a neighbouring (x, y) row collides with one that stayed).  Measured and NOT adopted: PZ = 48 -
-    // rows half of the banks apart - runs the bare atomics 1.29x faster (scripts/micro/lds_tile_atomics.hip: 335 -> 433 G
-    // particles/s; 32-bit cells 543, a 32-bit lo plane with returning adds + carry into a hi plane 377), but the 31 KB
-    // tile leaves 5 workgroups per CU instead of 7 and the walk gets slower: CIC 4.62 -> 4.71 ms (TSC 13.1 -> 12.3).
-#ifndef WALK_PZ
-#define WALK_PZ 0
-#endif
-    // WALK_ODD_PITCH (measured, not adopted): row pitches odd, in cells, for both neighbour directions (y: PZ, x: LYP * PZ) so
-    // that, with the lanes of a half wave split even / odd (load_pos), a particle moved by one row lands on the banks of a
-    // cell of the other parity.  CIC's 33 and 9 * 33 are odd as they are; TSC (34, 10 rows) padded to 35 and 11 rows costs
-    // a workgroup of occupancy (33 KB) and gains nothing: 11.5 -> 11.6 ms.
-#ifndef WALK_ODD_PITCH
-#define WALK_ODD_PITCH 0
-#endif
-    constexpr int PZ = WALK_PZ > LZ ? WALK_PZ : (WALK_ODD_PITCH ? (LZ | 1) : LZ);
-    constexpr int LYP = WALK_ODD_PITCH ? (LY | 1) : LY;      // rows per x-plane of the tile (>= LY)
-    __shared__ unsigned long long tile[LX * LYP * PZ];       // ((a * LYP + b) * PZ + slot), slot fastest
-    auto trow = [](int ab) { return LYP == LY ? ab : (ab / LY) * LYP + ab % LY; };      // logical (a, b) pair -> row of the LDS tile
+    // Rows are packed: LY rows per x-plane, LZ cells per row.  The walk is bound by its LDS atomics (rocprofv3: LDS 77 % busy,
+    // 59 % of its cycles bank conflicts), and padded pitches were measured: 48 cells per row run the bare atomics 1.29x
+    // faster (scripts/micro/lds_tile_atomics.hip), but the 31 KB tile leaves 5 workgroups per CU instead of 7 and the walk
+    // gets slower (CIC 4.62 -> 4.71 ms); odd pitches in both directions cost TSC a workgroup of occupancy and gain nothing.
+    __shared__ unsigned long long tile[LX * LY * LZ];        // ((a * LY + b) * LZ + slot), slot fastest
     // the launch walks the columns col0 .. col0 + gridDim.x - 1 (mod the column count: the x-sorted pipeline's last
     // launch wraps around to the tile rows it held back)
     // nseg > 1: the column is cut into nseg z-segments of ntz / nseg tiles, one workgroup each (more, shorter
@@ -1286,7 +1272,7 @@ column_deposit_kernel(const T* __restrict__ pos, const T* __restrict__ mass, Til
     const int ox = tx * TX, oy = ty * TY;
     const bool x_periodic = g.nx_alloc == g.n;
     unsigned long long ndrop = 0;
-    for (int i = threadIdx.x; i < LX * LYP * PZ; i += 256) tile[i] = BIAS;
+    for (int i = threadIdx.x; i < LX * LY * LZ; i += 256) tile[i] = BIAS;
     // where the z line of LDS column (a, b) goes: the owned cells' grid line (bit 1 set: `offset`
     // is subtracted there, in double, before the one rounding to T) or the halo ring's record line
     // (bit 0: a halo that points outside a slab buffer, counted as dropped when non-zero);
@@ -1358,17 +1344,11 @@ column_deposit_kernel(const T* __restrict__ pos, const T* __restrict__ mass, Til
     // slots.  Nothing may be computed from the loaded values here: that would wait for them on the spot, and with
     // them for everything else in flight.  (A stray block re-reads the tile's last record, or the segment's first
     // slot when the tile has none: unconditional loads.)
-#ifndef WALK_LANE_PERM
-#define WALK_LANE_PERM 1
-#endif
-    // which of the batch's 32-particle entries (0 .. 7 per slot u) and which of its particles a lane takes:
-    //   0  half wave h = entry, lane = particle
-    //   1  half wave h = entry, lanes 0-15 the even particles, 16-31 the odd ones
-    //   2  the wave's two entries interleaved over its four 16-lane groups: group g holds the particles = g (mod 4) of both
-    const uint32_t lane6 = threadIdx.x & 63u, wave2 = (threadIdx.x >> 6) << 1;
-    const uint32_t my_entry = WALK_LANE_PERM == 2 ? wave2 + ((lane6 >> 3) & 1u) : (threadIdx.x >> 5);
-    const uint32_t my_part = WALK_LANE_PERM == 2 ? 4u * (lane6 & 7u) + (lane6 >> 4)
-                           : WALK_LANE_PERM == 1 ? (((lane6 & 15u) << 1) | ((lane6 >> 4) & 1u)) : (lane6 & 31u);
+    // which of the batch's 32-particle entries (0 .. 7 per slot u) and which of its particles a lane takes: half wave h =
+    // entry, lanes 0-15 the even particles, 16-31 the odd ones (see load_pos)
+    const uint32_t lane6 = threadIdx.x & 63u;
+    const uint32_t my_entry = threadIdx.x >> 5;
+    const uint32_t my_part = ((lane6 & 15u) << 1) | ((lane6 >> 4) & 1u);
     auto load_idx = [&](const Batch& bt, GroupRec (&rec)[U]) {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -1394,7 +1374,7 @@ column_deposit_kernel(const T* __restrict__ pos, const T* __restrict__ mass, Til
                 // lane -> particle of the 32-particle entry: lanes 0-15 take the even particles, 16-31 the odd ones.  In
                 // z-ordered input the particles of a window sit in consecutive cells; a particle that the jitter moved
                 // to a neighbouring (x, y) row lands one cell (y) or nine (x) further in the banks - on the banks of
-                // an ODD neighbour, which is now in the other half of the lanes (WALK_LANE_PERM 0: identity)
+                // an ODD neighbour, which is now in the other half of the lanes
                 const uint32_t r = bt.i0 + u * 8 + my_entry, b = my_part;
                 const bool st = r >= bt.nrec;                                   // uniform per half wave
                 const uint32_t sidx = (r - bt.nrec) * 32u + b;
@@ -1475,7 +1455,7 @@ column_deposit_kernel(const T* __restrict__ pos, const T* __restrict__ mass, Til
             int sl = lz + sh;
             sl = sl >= LZ ? sl - LZ : sl;
             // (24-bit multiplies: the plain expression compiles to a quarter-rate v_mad_u64_u32 and v_mul_lo_u32 per particle)
-            unsigned long long* const row0 = &tile[__umul24(__umul24((unsigned)lx, (unsigned)LYP) + (unsigned)ly, (unsigned)PZ)];
+            unsigned long long* const row0 = &tile[__umul24(__umul24((unsigned)lx, (unsigned)LY) + (unsigned)ly, (unsigned)LZ)];
 #pragma unroll
             for (int c = 0; c < W; ++c) {
                 slot[c] = row0 + sl;
@@ -1491,7 +1471,7 @@ column_deposit_kernel(const T* __restrict__ pos, const T* __restrict__ mass, Til
                     for (int c = 0; c < W; ++c) {
                         long long v = __double_as_longlong(__fma_rn(mab, wz[c], 6755399441055744.0));   // |mab wz| < 2^50
                         if (!RAW) v -= 0x4338000000000000ll;
-                        unsigned long long* cell = slot[c] + (a * LYP + b) * PZ;
+                        unsigned long long* cell = slot[c] + (a * LY + b) * LZ;
                         if (ablate & 2) asm volatile("" ::"v"(v), "v"(cell)); else atomicAdd(cell, (unsigned long long)v);
                     }
                 }
@@ -1546,8 +1526,8 @@ column_deposit_kernel(const T* __restrict__ pos, const T* __restrict__ mass, Til
                 bool any = false;
 #pragma unroll
                 for (int i = 0; i < VW; ++i) {
-                    const unsigned long long raw = tile[trow(ab) * PZ + sl[i]];
-                    tile[trow(ab) * PZ + sl[i]] = BIAS;
+                    const unsigned long long raw = tile[ab * LZ + sl[i]];
+                    tile[ab * LZ + sl[i]] = BIAS;
                     any |= raw != BIAS;
                     if (ftz == 0 && c0 + i < H) first_planes[ab * H + c0 + i] = raw;     // (stored below, rewritten at the end)
                     if (RAW) {
@@ -1633,7 +1613,7 @@ column_deposit_kernel(const T* __restrict__ pos, const T* __restrict__ mass, Til
             int sl = k + sh;
             sl = sl >= LZ ? sl - LZ : sl;
             zf[i] = first_planes[i];
-            zf[LX * LY * H + i] = tile[trow(ab) * PZ + sl];
+            zf[LX * LY * H + i] = tile[ab * LZ + sl];
         }
         if (dropped && ndrop) atomicAdd(dropped, ndrop);
         return;
@@ -1642,7 +1622,7 @@ column_deposit_kernel(const T* __restrict__ pos, const T* __restrict__ mass, Til
         const int k = i % H, ab = i / H;
         int sl = k + sh;
         sl = sl >= LZ ? sl - LZ : sl;
-        const unsigned long long raw = first_planes[i] + tile[trow(ab) * PZ + sl] - BIAS;
+        const unsigned long long raw = first_planes[i] + tile[ab * LZ + sl] - BIAS;
         const unsigned long long d = dest[ab];
         bool any;
         const T v = fixed_to_value<T>(raw, q, (d & 2ull) ? offset : 0.0, any);
@@ -1689,33 +1669,6 @@ z_seam_kernel(const unsigned long long* __restrict__ zrec, TileGeom g, double sc
     }
     if (dropped && ndrop) atomicAdd(dropped, ndrop);
 }
-
-#ifdef PAINT_WALK_TEST
-// perf experiment: the plainest possible walk over a column's index lists and positions
-template <typename T>
-__global__ void __launch_bounds__(256)
-walk_test_kernel(const T* __restrict__ pos, TileGeom g, const uint32_t* __restrict__ index,
-                 const uint32_t* __restrict__ tile_count, uint32_t cap, T* out) {
-    __shared__ T pad[5400];
-    T acc = 0;
-    for (int tz = 0; tz < g.ntz; ++tz) {
-        const uint32_t t = blockIdx.x * g.ntz + tz;
-        const uint32_t cnt = min(tile_count[t], cap);
-        const size_t off = (size_t)t * cap;
-        for (uint32_t i0 = 0; i0 < cnt; i0 += 1024) {
-            uint32_t idx[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) idx[u] = index[off + min(i0 + u * 256 + threadIdx.x, cnt - 1)];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const size_t q = (size_t)idx[u] * 3;
-                acc += pos[q] + pos[q + 1] + pos[q + 2];
-            }
-        }
-    }
-    if (acc == (T)1234.5) { out[0] = acc; pad[threadIdx.x] = acc; out[1] = pad[(threadIdx.x * 7) % 5400]; }
-}
-#endif
 
 // Every column adds its neighbours' halo records into its own border rows.  Only the border cells
 // have anything to add (15 of 64 for CIC, 28 for TSC), each from at most 3 neighbours: a small
@@ -1808,10 +1761,35 @@ struct StageSel {
     int closed_row0 = 0, closed_nrows = 0;        // GROUP_PART: tile rows already walked (a range that may wrap around)
 };
 
+// TEST HOOKS.  Four environment variables force paths that the code otherwise selects from the geometry and the size.
+// They are read here and nowhere else, once per C-ABI call (the tests change them between calls):
+//   AST_PAINT_ZSEG          z-segments per column of the walk (test_z_segmented_walk_is_bit_identical)
+//   AST_PAINT_XCHUNK_MB     chunk size of the x-sorted pipeline in MB of positions, and
+//   AST_PAINT_XSTREAMS      its streams, 1 | 2 (test_xsorted_pipeline_matches_plain_paint)
+//   AST_PAINT_LATE_LDS_MIN  late-list length from which the scatter path deposits the list through LDS tiles
+//                           (test_scattered_path_two_level_bucket_scatter, tests/test_gpu_paint_paths.py)
+// The first three enter the walk plan, and through its z-segments the workspace size (tests/test_paint_layout_cpu.py).
+struct TestHooks {
+    static constexpr int UNSET = INT_MIN;
+    int zseg = UNSET, xchunk_mb = UNSET, xstreams = UNSET;
+    bool late_lds_set = false;
+    unsigned long long late_lds_min = 0;
+    static int or_default(int v, int dflt) { return v == UNSET ? dflt : v; }
+};
+TestHooks read_test_hooks() {
+    TestHooks h;
+    const char* v;
+    auto set = [&v](const char* name) { v = getenv(name); return v != nullptr; };
+    if (set("AST_PAINT_ZSEG")) h.zseg = atoi(v);
+    if (set("AST_PAINT_XCHUNK_MB")) h.xchunk_mb = atoi(v);
+    if (set("AST_PAINT_XSTREAMS")) h.xstreams = atoi(v);
+    if ((h.late_lds_set = set("AST_PAINT_LATE_LDS_MIN"))) h.late_lds_min = strtoull(v, nullptr, 10);
+    return h;
+}
+
 // How the single-pass overwrite paint is cut up: z-segments per column (walk workgroups = columns x nseg) and, with
-// AST_PAINT_XSORTED, chunks of `chunk_planes` buffer planes' worth of particles.  A function of the geometry, np and
-// the flags only (the workspace is sized from it); AST_PAINT_ZSEG / AST_PAINT_XCHUNK_MB / AST_PAINT_XMARGIN /
-// AST_PAINT_XSTREAMS override it for experiments.
+// AST_PAINT_XSORTED, chunks of `chunk_planes` buffer planes' worth of particles.  A function of the geometry, np, the
+// flags and the test hooks only (the workspace is sized from it).
 struct WalkPlan {
     int nseg;            // z-segments per column (divides ntz)
     int chunks;          // 1: not chunked
@@ -1819,13 +1797,12 @@ struct WalkPlan {
     int margin_planes;   // a tile row is walked once the chunks cover its planes plus this many
     int streams;         // 2: the walks run on a second stream beside the grouping of the next chunks
 };
-inline int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
 inline int seg_count(int want, int ntz) {            // largest divisor of ntz that is a power of two <= want
     int n = 1;
     while (n * 2 <= want && ntz % (n * 2) == 0) n *= 2;
     return n;
 }
-inline WalkPlan walk_plan(const TileGeom& g, size_t np, int flags, size_t esz) {
+inline WalkPlan walk_plan(const TileGeom& g, size_t np, int flags, size_t esz, const TestHooks& hooks) {
     WalkPlan p{1, 1, g.nx_alloc, 0, 1};
     if ((flags & AST_PAINT_TWO_PASS) || !(flags & AST_PAINT_OVERWRITE)) return p;
     const unsigned ncols = (unsigned)(g.ntx * g.nty);
@@ -1837,15 +1814,15 @@ inline WalkPlan walk_plan(const TileGeom& g, size_t np, int flags, size_t esz) {
         // 256 MB Infinity Cache when the walk gathers it - launches of ~1000 workgroups are bound by their tails:
         // 13.5-20.7 ms, grouping 5.8-10.8 and walks 6.0 where the two big launches take 3.7 + 4.7.
         const double plane_bytes = (double)np * 3.0 * (double)esz / (double)g.nx_alloc;
-        const int mb = env_int("AST_PAINT_XCHUNK_MB", 0);
+        const int mb = TestHooks::or_default(hooks.xchunk_mb, 0);
         int cp = mb > 0 ? (int)(1048576.0 * (double)mb / plane_bytes + 0.5) : (g.nx_alloc + 3) / 4;
         cp = std::max(2, std::min(cp, g.nx_alloc));
         const int K = (g.nx_alloc + cp - 1) / cp;
         if (K >= 2 && g.ntx >= 4 * K / 2 && np >= (size_t)K * 16 * 4096) {
             p.chunks = K;
             p.chunk_planes = cp;
-            p.margin_planes = env_int("AST_PAINT_XMARGIN", g.nx_alloc == g.n ? 4 : 12);
-            p.streams = env_int("AST_PAINT_XSTREAMS", mb > 0 ? 1 : 2);
+            p.margin_planes = g.nx_alloc == g.n ? 4 : 12;
+            p.streams = TestHooks::or_default(hooks.xstreams, mb > 0 ? 1 : 2);
             rows_per_launch = std::max(1, cp / TX);
         }
     }
@@ -1854,7 +1831,7 @@ inline WalkPlan walk_plan(const TileGeom& g, size_t np, int flags, size_t esz) {
     int want = 1;
     if (p.chunks > 1) { while (per_launch * (unsigned)want < 2048u && want < 16) want *= 2; }
     else if (ncols < 4096u) { while (ncols * (unsigned)want < 8192u && want < 8) want *= 2; }
-    p.nseg = seg_count(env_int("AST_PAINT_ZSEG", want), g.ntz);
+    p.nseg = seg_count(TestHooks::or_default(hooks.zseg, want), g.ntz);
     return p;
 }
 
@@ -1883,6 +1860,8 @@ struct Workspace {
     uint32_t tpb;                    // tiles per bucket (0: the scatter path does not apply)
     uint32_t nb;                     // buckets (scatter_buckets)
     uint32_t* late_index;            // record numbers of the late list, tile-major (its deposit through LDS tiles)
+    uint32_t ntiles, ncols;          // of the geometry
+    WalkPlan plan;                   // the workspace is sized for this plan
     size_t bytes;
 };
 
@@ -1900,70 +1879,75 @@ inline uint32_t tile_capacity(size_t np, uint32_t ntiles) {
     return (uint32_t)(cap > 0x7fffffffull ? 0x7fffffffull : cap);
 }
 
-// flags decide the list format: two pass -> exact id lists; single pass -> fixed-capacity id segments, or
-// (with AST_PAINT_OVERWRITE) the compact group / stray lists.  A tile's group segment holds cap / MINPOP records
-// (enough for `cap` particles however they are grouped), its stray segment cap / 4 copies - or `cap` with
-// AST_PAINT_SCATTERED, for input without spatial order where every particle is a stray.
 // Buckets of the two-level scatter: the power of two nearest to sqrt(ntiles) from above, in [64, SC_BUCKETS_MAX] - both
 // levels then split into about equally many destinations (1024^3: 524288 tiles -> 1024 buckets of 512 tiles; 512 buckets of
 // 1024 measure the same within 1 %) - and enough of them that a bucket's tiles fit level B's tables.
-// AST_PAINT_SC_BUCKETS overrides (experiments; a multiple of 8).
 uint32_t scatter_buckets(uint32_t ntiles) {
-    static const uint32_t forced = [] { const char* v = getenv("AST_PAINT_SC_BUCKETS"); return v ? (uint32_t)atoi(v) : 0u; }();
-    if (forced >= 8 && forced <= SC_BUCKETS_MAX && forced % 8 == 0) return forced;
     uint32_t nb = 64;
     while (nb < SC_BUCKETS_MAX && ((unsigned long long)nb * nb < ntiles || (ntiles + nb - 1) / nb > SC_TPB_MAX)) nb <<= 1;
     return nb;
 }
 
-Workspace carve(void* base, size_t np, uint32_t ntiles, uint32_t ncols, int flags, size_t esz, size_t rec_bytes, size_t zrec_bytes = 0) {
+// THE workspace layout: where everything lies inside `base` (nullptr: only the byte count is wanted), the capacities of
+// the lists and the walk plan the seam area is sized for.  Every C-ABI entry goes through here - ast_fft_tile_power_3d_halo
+// reads the halo records where ast_paint_tiled_halo finds `rec` - and tests/test_paint_layout_cpu.py pins the result.
+// flags decide the list format: two pass -> exact id lists; single pass -> fixed-capacity id segments, or
+// (with AST_PAINT_OVERWRITE) the compact group / stray lists.  A tile's group segment holds cap / MINPOP records
+// (enough for `cap` particles however they are grouped), its stray segment cap / 4 copies - or `cap` with
+// AST_PAINT_SCATTERED, for input without spatial order where every particle is a stray.
+Workspace paint_layout(void* base, int window, size_t esz, size_t np, const TileGeom& g, int flags, const TestHooks& hooks) {
     const bool two_pass = (flags & AST_PAINT_TWO_PASS) != 0;
     const bool compact = !two_pass && (flags & AST_PAINT_OVERWRITE);
     Workspace w;
+    w.plan = walk_plan(g, np, flags, esz, hooks);
+    w.ncols = (uint32_t)(g.ntx * g.nty);
+    w.ntiles = w.ncols * (uint32_t)g.ntz;
+    const size_t ntiles = w.ntiles;
     size_t off = 0;
     auto take = [&](size_t bytes) { void* p = (char*)base + off; off += align256(bytes); return p; };
     w.ovf_count = (unsigned long long*)take(8);
-    w.col_flags = (uint32_t*)take((size_t)ncols * 4);
-    w.tile_count = (uint32_t*)take((size_t)ntiles * 4);
-    w.tile_fill = (uint32_t*)take((size_t)ntiles * 4);
-    w.fill64 = (unsigned long long*)take(compact ? (size_t)ntiles * 8 : 0);
+    w.col_flags = (uint32_t*)take((size_t)w.ncols * 4);
+    w.tile_count = (uint32_t*)take(ntiles * 4);
+    w.tile_fill = (uint32_t*)take(ntiles * 4);
+    w.fill64 = (unsigned long long*)take(compact ? ntiles * 8 : 0);
     const bool scattered = compact && (flags & AST_PAINT_SCATTERED);
-    w.nb = scatter_buckets(ntiles);
-    w.tpb = scattered ? (ntiles + w.nb - 1) / w.nb : 0;
+    w.nb = scatter_buckets(w.ntiles);
+    w.tpb = scattered ? (w.ntiles + w.nb - 1) / w.nb : 0;
     if (w.tpb > SC_TPB_MAX || np < (size_t)8192) w.tpb = 0;      // huge grids / tiny inputs: the grouping kernel does it
-    w.bcursor = (unsigned long long*)take(w.tpb ? (size_t)w.nb * SC_GROUPS * 8 : 0);      // (inside the part run_tiled zeroes)
+    w.bcursor = (unsigned long long*)take(w.tpb ? (size_t)w.nb * SC_GROUPS * 8 : 0);      // (inside the part TiledPaint::run zeroes)
     // a (bucket, label) segment holds twice its mean share of the particles
     w.cap_bg = w.tpb ? (uint32_t)((2 * ((np + (size_t)w.nb * SC_GROUPS - 1) / ((size_t)w.nb * SC_GROUPS)) + 1024 + 63) / 64 * 64) : 0;
     w.late = (unsigned long long*)take(w.tpb ? 8 : 0);
-    w.tile_off = (uint32_t*)take((size_t)ntiles * 4);
+    w.tile_off = (uint32_t*)take(ntiles * 4);
     w.block_sums = (uint32_t*)take((size_t)((ntiles + 1023) / 1024 + 1) * 4);
-    w.cap = two_pass ? 0 : tile_capacity(np, ntiles);
+    w.cap = two_pass ? 0 : tile_capacity(np, w.ntiles);
     w.rcap = compact && !w.tpb ? (w.cap + MINPOP - 1) / MINPOP : 0;       // the scatter path writes stray copies only
     w.scap = compact ? ((flags & AST_PAINT_SCATTERED) ? w.cap : (w.cap + 3) / 4) : 0;
-    {   // At 1024^3 a tile's record segment is 512 x 8 bytes and its stray segment 1024 x 12: strides of 4 KB and 12 KB, so every
-        // segment starts at the same offset inside a 4-KB block and the grouping kernel's stores crowd a few channels - how
-        // badly depends on where the workspace's pages lie (the step's 12.6-13.1 ms spread).  16 records / 32 copies more per
-        // segment make the strides odd multiples of 128 bytes: grouping 3.61 -> 3.46 ms, step 12.95 -> 12.79 (means over ten
-        // placements each, scripts/micro/placement_step.py; AST_PAINT_SEG_SKEW=0 restores the old strides).
-        static const int skew = getenv("AST_PAINT_SEG_SKEW") ? atoi(getenv("AST_PAINT_SEG_SKEW")) : 1;
-        if (skew && w.rcap) w.rcap += 16 * skew;
-        if (skew && w.scap) w.scap += 32 * skew;
-        // (the scatter path: level B's stores into the stray segments 5.7 -> 5.5 ms; level A's staging segments - 3 MB apart -
-        // measured worse with such a skew, 6.6 -> 6.8, and keep their stride)
-    }
-    w.index = (uint32_t*)take(two_pass ? np * 4 : compact ? 0 : (size_t)ntiles * w.cap * 4);
-    w.recs = (GroupRec*)take((size_t)ntiles * w.rcap * sizeof(GroupRec));
-    w.strays = take((size_t)ntiles * w.scap * 4 * esz);
+    // At 1024^3 a tile's record segment is 512 x 8 bytes and its stray segment 1024 x 12: strides of 4 KB and 12 KB, so every
+    // segment starts at the same offset inside a 4-KB block and the grouping kernel's stores crowd a few channels - how
+    // badly depends on where the workspace's pages lie (the step's 12.6-13.1 ms spread).  16 records / 32 copies more per
+    // segment make the strides odd multiples of 128 bytes: grouping 3.61 -> 3.46 ms, step 12.95 -> 12.79 (means over ten
+    // placements each, scripts/micro/placement_step.py).
+    // (the scatter path: level B's stores into the stray segments 5.7 -> 5.5 ms; level A's staging segments - 3 MB apart -
+    // measured worse with such a skew, 6.6 -> 6.8, and keep their stride)
+    if (w.rcap) w.rcap += 16;
+    if (w.scap) w.scap += 32;
+    w.index = (uint32_t*)take(two_pass ? np * 4 : compact ? 0 : ntiles * w.cap * 4);
+    w.recs = (GroupRec*)take(ntiles * w.rcap * sizeof(GroupRec));
+    w.strays = take(ntiles * w.scap * 4 * esz);
     w.staging = take(w.tpb ? (size_t)w.nb * SC_GROUPS * w.cap_bg * 4 * esz : 0);
     w.ovf = (uint32_t*)take(two_pass ? 0 : np * 4);
     w.late_index = (uint32_t*)take(w.tpb ? late_capacity(np, esz) * sizeof(uint32_t) : 0);      // one id per record the list has room for
-    w.rec = take(rec_bytes);
-    w.zrec = (unsigned long long*)take(zrec_bytes);
+    const bool tsc = window == AST_WIN_TSC;
+    const size_t ring = tsc ? RingMap<3>::COUNT : RingMap<2>::COUNT;
+    const size_t seam_cells = tsc ? (size_t)(TX + 2) * (TY + 2) * 2 : (size_t)(TX + 1) * (TY + 1);      // LX * LY * H
+    w.rec = take((flags & AST_PAINT_OVERWRITE) ? (size_t)w.ncols * ring * ast::rec_pitch((size_t)g.n) * esz : 0);
+    w.zrec = (unsigned long long*)take(w.plan.nseg > 1 ? (size_t)w.ncols * w.plan.nseg * 2 * seam_cells * sizeof(unsigned long long) : 0);
     w.bytes = off;
     return w;
 }
 
-bool tiled_geometry(int nmesh, int nx_alloc, TileGeom& g, uint32_t& ntiles) {
+bool tiled_geometry(int nmesh, int nx_alloc, TileGeom& g) {
     if (nmesh % TY || nmesh % TZ) return false;
     g.n = nmesh;
     g.nx_alloc = nx_alloc;
@@ -1971,162 +1955,298 @@ bool tiled_geometry(int nmesh, int nx_alloc, TileGeom& g, uint32_t& ntiles) {
     g.nty = nmesh / TY;
     g.ntz = nmesh / TZ;
     const unsigned long long nt = (unsigned long long)g.ntx * g.nty * g.ntz;
-    if (nt >= (1ull << 31) || (unsigned long long)g.ntx * g.nty >= (1ull << 24)) return false;      // (24-bit multiplies in tile_of)
-    ntiles = (uint32_t)nt;
-    return true;
+    return nt < (1ull << 31) && (unsigned long long)g.ntx * g.nty < (1ull << 24);      // (24-bit multiplies in tile_of)
 }
 
-inline size_t seam_bytes(int window, const TileGeom& g, size_t np, size_t esz, int flags) {
-    const WalkPlan p = walk_plan(g, np, flags, esz);
-    if (p.nseg <= 1) return 0;
-    const size_t cells = window == AST_WIN_TSC ? (size_t)(TX + 2) * (TY + 2) * 2 : (size_t)(TX + 1) * (TY + 1);
-    return (size_t)g.ntx * g.nty * p.nseg * 2 * cells * sizeof(unsigned long long);
-}
-
-inline size_t record_bytes(int window, const TileGeom& g, size_t esz, int flags) {
-    if (!(flags & AST_PAINT_OVERWRITE)) return 0;
-    const size_t ring = window == AST_WIN_TSC ? RingMap<3>::COUNT : RingMap<2>::COUNT;
-    return (size_t)g.ntx * g.nty * ring * ast::rec_pitch((size_t)g.n) * esz;
-}
-
+// One call of ast_paint_tiled / ast_paint_tiled_stage: its arguments, the geometry, the workspace with its plan and the
+// stream; the launch helpers, each written once, and on top of them one function per path.
 template <typename T, int W>
-int run_tiled(const T* pos, const T* mass, size_t np, TileGeom g, uint32_t ntiles, double scale, T* grid,
-              void* workspace, unsigned long long* dropped, int flags, double mass_bound, double offset, hipStream_t s,
-              StageSel sel = StageSel{}) {
-    const bool two_pass = (flags & AST_PAINT_TWO_PASS) != 0;
-    const bool overwrite = (flags & AST_PAINT_OVERWRITE) != 0;
-    const unsigned ncols = (unsigned)(g.ntx * g.nty);
-    const WalkPlan plan = walk_plan(g, np, flags, sizeof(T));
-    Workspace w = carve(workspace, np, ntiles, ncols, flags, sizeof(T),
-                        record_bytes(W == 3 ? AST_WIN_TSC : AST_WIN_CIC, g, sizeof(T), flags),
-                        seam_bytes(W == 3 ? AST_WIN_TSC : AST_WIN_CIC, g, np, sizeof(T), flags));
-    // ovf_count, col_flags, tile_count, tile_fill and fill64 are contiguous at the front of the workspace
-    if (sel.stage == AST_PAINT_STAGE_ALL || sel.stage == AST_PAINT_STAGE_GROUP || sel.stage == AST_PAINT_STAGE_RESET)
-        AST_CHECK_HIP(hipMemsetAsync(w.ovf_count, 0, (size_t)((char*)w.tile_off - (char*)w.ovf_count), s));
-    const size_t per_interval = (size_t)256 * IDX_UNROLL * AGG_TRIPS;
-    const size_t nintervals = (np + per_interval - 1) / per_interval;
-    // grid of the index pass: ONE interval per workgroup.  Measured at 1024^3: 8192 workgroups of 32
+struct TiledPaint {
+    const T *pos, *mass;
+    size_t np;
+    TileGeom g;
+    double scale;
+    T* grid;
+    unsigned long long* dropped;
+    int flags;
+    double mass_bound, offset;
+    hipStream_t s;
+    TestHooks hooks;
+    Workspace w;
+    WalkPlan plan = w.plan;
+    uint32_t ntiles = w.ntiles;
+    unsigned ncols = w.ncols;
+    bool two_pass = (flags & AST_PAINT_TWO_PASS) != 0;
+    bool overwrite = (flags & AST_PAINT_OVERWRITE) != 0;
+    bool plainx = g.x_start == 0 && g.nx_alloc == g.n;
+    static constexpr size_t per_interval = (size_t)256 * IDX_UNROLL * AGG_TRIPS;
+    // index and grouping passes: ONE interval per workgroup.  Measured at 1024^3: 8192 workgroups of 32
     // intervals 4.72 ms, 65536 x 4: 4.40, 262144 x 1: 4.28; persistent grids of a few per CU are the
     // slowest (4.95-5.0): short workgroups keep the CUs' phases mixed and leave no ragged last round.
-    // (The kernel still loops, for inputs beyond 2^31 intervals and for AST_PAINT_INDEX_GRID experiments.)
-    const size_t want = getenv("AST_PAINT_INDEX_GRID") ? (size_t)atol(getenv("AST_PAINT_INDEX_GRID")) : (size_t)0x7fffffff;
-    const unsigned ga = (unsigned)(nintervals > want ? want : nintervals);
-    const bool plainx = g.x_start == 0 && g.nx_alloc == g.n;
-    auto index_pass = [&](auto mode, uint32_t* tile_count, const uint32_t* tile_off, uint32_t* tile_fill, uint32_t* index,
-                          uint32_t cap, uint32_t* ovf, unsigned long long* ovf_count, unsigned long long* drop) {
-        constexpr int MODE = decltype(mode)::value;
+    // (The kernels still loop, for inputs beyond 2^31 intervals.)
+    static unsigned interval_grid(size_t n, size_t most = 0x7fffffff) {
+        const size_t nint = (n + per_interval - 1) / per_interval;
+        return (unsigned)(nint > most ? most : nint);
+    }
+    unsigned long long late_cap() const { return late_capacity(np, sizeof(T)); }       // the overflow list's room
+
+    // ---- launch helpers ----  (their order here is the order of the kernels in the code object: see the instantiations below)
+    // AST_PAINT_SCATTERED: the two bucket levels (particles -> staging -> the tiles' stray segments)
+    template <bool PX, int SW>
+    int scatter_levels_as() {
+        const unsigned nchunks = (unsigned)((np + SCA_THREADS * SC_PER_THREAD - 1) / (SCA_THREADS * SC_PER_THREAD));
+        const size_t lds_a = sc_round<T, SCA_THREADS>() * (SW * sizeof(T) + sizeof(unsigned long long));
+        const size_t lds_b = sc_round<T, SCB_THREADS>() * (SW * sizeof(T) + sizeof(unsigned long long)) + (size_t)((w.tpb + 1u) & ~1u) * 20;
+        const size_t lds_b_max = sc_round<T, SCB_THREADS>() * (SW * sizeof(T) + sizeof(unsigned long long)) + (size_t)SC_TPB_MAX * 20;
+        static ast::PerDeviceOnce attr_once;
+        if (attr_once.need()) {
+            AST_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&scatter_level_a_kernel<T, W, PX, SW>),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a));
+            AST_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&scatter_level_b_kernel<T, W, PX, SW>),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b_max));
+            attr_once.mark();
+        }
+        {
+            AST_PROF("paint_tiled.level_a", s);
+            scatter_level_a_kernel<T, W, PX, SW><<<nchunks, SCA_THREADS, lds_a, s>>>(
+                pos, mass, np, g, w.tpb, w.nb, w.bcursor, (T*)w.staging, w.cap_bg, w.col_flags, (T*)w.ovf, late_cap(), w.late, dropped);
+        }
+        AST_PROF("paint_tiled.level_b", s);
+        scatter_level_b_kernel<T, W, PX, SW><<<w.nb * SCB_WGS, SCB_THREADS, lds_b, s>>>(
+            (const T*)w.staging, w.bcursor, w.cap_bg, g, w.tpb, w.nb, w.fill64, (T*)w.strays, w.scap, (T*)w.ovf, late_cap(), w.late, dropped);
+        return AST_OK;
+    }
+    int scatter_levels() {
+        if (mass) return plainx ? scatter_levels_as<true, 4>() : scatter_levels_as<false, 4>();
+        return plainx ? scatter_levels_as<true, 3>() : scatter_levels_as<false, 3>();      // no masses: 3-word records
+    }
+    // the index kernel over the n records of src (STRIDE words each); n_dev / n_min: see tile_index_kernel
+    template <int MODE, int STRIDE = 3>
+    void index_pass(const T* src, size_t n, unsigned wgs, uint32_t* tile_count, const uint32_t* tile_off, uint32_t* tile_fill,
+                    uint32_t* index, uint32_t cap, uint32_t* ovf, unsigned long long* ovf_count, unsigned long long* drop,
+                    const unsigned long long* n_dev = nullptr, unsigned long long n_min = 0) {
         if (plainx)
-            tile_index_kernel<T, W, MODE, true><<<ga, 256, 0, s>>>(pos, np, g, tile_count, tile_off, tile_fill, index, cap, ovf,
-                                                                   ovf_count, w.col_flags, drop);
+            tile_index_kernel<T, W, MODE, true, STRIDE><<<wgs, 256, 0, s>>>(src, n, g, tile_count, tile_off, tile_fill, index, cap, ovf,
+                                                                            ovf_count, w.col_flags, drop, n_dev, n_min);
         else
-            tile_index_kernel<T, W, MODE, false><<<ga, 256, 0, s>>>(pos, np, g, tile_count, tile_off, tile_fill, index, cap, ovf,
-                                                                    ovf_count, w.col_flags, drop);
-    };
+            tile_index_kernel<T, W, MODE, false, STRIDE><<<wgs, 256, 0, s>>>(src, n, g, tile_count, tile_off, tile_fill, index, cap, ovf,
+                                                                             ovf_count, w.col_flags, drop, n_dev, n_min);
+    }
+    // exclusive scan of tile_count into tile_off
+    void tile_scan() {
+        const uint32_t nblk = (ntiles + 1023) / 1024;
+        scan_blocks_kernel<<<nblk, 256, 0, s>>>(w.tile_count, w.tile_off, w.block_sums, ntiles);
+        scan_sums_kernel<<<1, 256, 0, s>>>(w.block_sums, nblk);
+        scan_add_kernel<<<nblk, 256, 0, s>>>(w.tile_off, w.block_sums, ntiles);
+    }
     // the column walk over the columns col0 .. col0 + ncol - 1 (mod ncols) on stream st
-    auto walk_pass = [&](const uint32_t* tile_off, const uint32_t* tile_count, int col0, unsigned ncol, hipStream_t st) {
+    void walk(const uint32_t* tile_off, const uint32_t* tile_count, int col0, unsigned ncol, hipStream_t st) {
         AST_PROF("paint_tiled.deposit", st);
         WalkCaps wl{w.rcap, w.scap, w.cap, np};
-        using I2 = std::integral_constant<int, 2>;
-        const int nseg = two_pass ? 1 : plan.nseg;
         auto launch = [&](auto has_mass, auto fmt) {
-            column_deposit_kernel<T, W, decltype(has_mass)::value, decltype(fmt)::value><<<ncol * (unsigned)nseg, 256, 0, st>>>(
+            column_deposit_kernel<T, W, decltype(has_mass)::value, decltype(fmt)::value><<<ncol * (unsigned)plan.nseg, 256, 0, st>>>(
                 pos, mass, g, scale, w.index, tile_off, tile_count, w.fill64, w.recs, (const T*)w.strays, wl,
-                mass ? mass_bound : 1.0, w.col_flags, grid, (T*)w.rec, offset, dropped, col0, nseg, w.zrec);
+                mass ? mass_bound : 1.0, w.col_flags, grid, (T*)w.rec, offset, dropped, col0, plan.nseg, w.zrec);
         };
         using I0 = std::integral_constant<int, 0>;
         using I1 = std::integral_constant<int, 1>;
+        using I2 = std::integral_constant<int, 2>;
         if (two_pass) { if (mass) launch(std::true_type{}, I0{}); else launch(std::false_type{}, I0{}); }
         else if (mass) launch(std::true_type{}, I1{});
         else launch(std::false_type{}, I2{});                     // no masses: 3-word stray copies
-    };
-    // the seams of a z-segmented walk (all columns, after their walks), then the x / y halo fold
-    auto fold_pass = [&]() {
-        if (!two_pass && plan.nseg > 1) {
-            AST_PROF("paint_tiled.seams", s);
-            z_seam_kernel<T, W><<<ncols, 256, 0, s>>>(w.zrec, g, scale, (uint32_t)std::min<unsigned long long>(5ull * w.cap, 0x3fffffffull),
-                                                       mass ? mass_bound : 1.0, grid, (T*)w.rec, offset, dropped, 0, plan.nseg);
-        }
-        if (!(flags & AST_PAINT_DEFER_FOLD)) {
-            AST_PROF("paint_tiled.fold", s);
-            column_fold_kernel<T, W><<<ncols, 256, 0, s>>>((const T*)w.rec, g, grid, 0);
-        }
-    };
-    auto deposit_pass = [&](const uint32_t* tile_off, const uint32_t* tile_count, uint32_t cap) {
+    }
+    // the seams of a z-segmented walk of these columns (after their walks)
+    void seams(int col0, unsigned ncol) {
+        if (plan.nseg <= 1) return;                               // (two pass: always)
+        AST_PROF("paint_tiled.seams", s);
+        z_seam_kernel<T, W><<<ncol, 256, 0, s>>>(w.zrec, g, scale, (uint32_t)std::min<unsigned long long>(5ull * w.cap, 0x3fffffffull),
+                                                  mass ? mass_bound : 1.0, grid, (T*)w.rec, offset, dropped, col0, plan.nseg);
+    }
+    // the x / y halo fold of these columns
+    void fold(int col0, unsigned ncol) {
+        AST_PROF("paint_tiled.fold", s);
+        column_fold_kernel<T, W><<<ncol, 256, 0, s>>>((const T*)w.rec, g, grid, col0);
+    }
+    // all columns have been walked: their seams, then the fold unless the caller's FFT does it
+    void seams_and_fold() {
+        seams(0, ncols);
+        if (!(flags & AST_PAINT_DEFER_FOLD)) fold(0, ncols);
+    }
+    // the lists are complete: column walk + seams + fold, or (accumulating paint) one workgroup per tile with global atomics
+    void deposit(const uint32_t* tile_off, const uint32_t* tile_count, uint32_t cap) {
         if (overwrite) {
-            walk_pass(tile_off, tile_count, 0, ncols, s);
-            fold_pass();
+            walk(tile_off, tile_count, 0, ncols, s);
+            seams_and_fold();
         } else {
             AST_PROF("paint_tiled.deposit", s);
             tile_deposit_kernel<T, W><<<ntiles, 256, 0, s>>>(pos, mass, g, scale, w.index, tile_off, tile_count, cap, grid, dropped);
         }
-    };
-    // AST_PAINT_SCATTERED: the two bucket levels (particles -> staging -> the tiles' stray segments)
-    auto scatter_pass = [&]() -> int {
-    {
-        const unsigned nchunks = (unsigned)((np + SCA_THREADS * SC_PER_THREAD - 1) / (SCA_THREADS * SC_PER_THREAD));
-        auto run = [&](auto px, auto sw) -> int {
-            constexpr bool PX = decltype(px)::value;
-            constexpr int SW = decltype(sw)::value;
-            const size_t lds_a = sc_round<T, SCA_THREADS>() * (SW * sizeof(T) + sizeof(unsigned long long));
-            const size_t lds_b = sc_round<T, SCB_THREADS>() * (SW * sizeof(T) + sizeof(unsigned long long)) + (size_t)((w.tpb + 1u) & ~1u) * 20;
-            const size_t lds_b_max = sc_round<T, SCB_THREADS>() * (SW * sizeof(T) + sizeof(unsigned long long)) + (size_t)SC_TPB_MAX * 20;
-            static ast::PerDeviceOnce attr_once;
-            if (attr_once.need()) {
-                AST_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&scatter_level_a_kernel<T, W, PX, SW>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a));
-                AST_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&scatter_level_b_kernel<T, W, PX, SW>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b_max));
-                attr_once.mark();
-            }
-            const unsigned long long late_cap = late_capacity(np, sizeof(T));       // the overflow list's room
-            {
-                AST_PROF("paint_tiled.level_a", s);
-                scatter_level_a_kernel<T, W, PX, SW><<<nchunks, SCA_THREADS, lds_a, s>>>(
-                    pos, mass, np, g, w.tpb, w.nb, w.bcursor, (T*)w.staging, w.cap_bg, w.col_flags, (T*)w.ovf, late_cap, w.late, dropped);
-            }
-            AST_PROF("paint_tiled.level_b", s);
-            scatter_level_b_kernel<T, W, PX, SW><<<w.nb * SCB_WGS, SCB_THREADS, lds_b, s>>>(
-                (const T*)w.staging, w.bcursor, w.cap_bg, g, w.tpb, w.nb, w.fill64, (T*)w.strays, w.scap, (T*)w.ovf, late_cap, w.late, dropped);
-            return AST_OK;
-        };
-        using S3 = std::integral_constant<int, 3>;
-        using S4 = std::integral_constant<int, 4>;
-        const int rc = mass ? (plainx ? run(std::true_type{}, S4{}) : run(std::false_type{}, S4{}))
-                            : (plainx ? run(std::true_type{}, S3{}) : run(std::false_type{}, S3{}));
-        if (rc != AST_OK) return rc;
     }
-        return AST_OK;
-    };
-    auto group_pass = [&](size_t pb, size_t pe, uint32_t closed_lo, uint32_t closed_n, uint32_t closed_mod = 0u) {
+    // compact lists of the particles [pb, pe); closed tiles: see tile_group_kernel (closed_mod is 0 for a whole periodic grid)
+    void group(size_t pb, size_t pe, uint32_t closed_lo, uint32_t closed_n, uint32_t closed_mod = 0u) {
         AST_PROF("paint_tiled.fill", s);
-        const size_t nint = (pe - pb + per_interval - 1) / per_interval;
-        static const unsigned xcd_map = getenv("AST_PAINT_GROUP_XCD") ? (unsigned)atoi(getenv("AST_PAINT_GROUP_XCD")) : 0u;
-        unsigned gg = (unsigned)(nint > want ? want : nint);
-        if (xcd_map && nint <= want && nint >= 64) gg = (gg + 7u) / 8u * 8u;          // (the map needs a multiple of 8; the surplus workgroups find no interval)
+        const unsigned gg = interval_grid(pe - pb);
         if (plainx)
             tile_group_kernel<T, W, true><<<gg, 256, 0, s>>>(pos, mass, pb, pe, g, w.fill64, w.recs, w.rcap, (T*)w.strays, w.scap,
-                                                             w.ovf, w.ovf_count, w.col_flags, dropped, closed_lo, closed_n, 0u, xcd_map);
+                                                             w.ovf, w.ovf_count, w.col_flags, dropped, closed_lo, closed_n, closed_mod);
         else
             tile_group_kernel<T, W, false><<<gg, 256, 0, s>>>(pos, mass, pb, pe, g, w.fill64, w.recs, w.rcap, (T*)w.strays, w.scap,
-                                                              w.ovf, w.ovf_count, w.col_flags, dropped, closed_lo, closed_n, closed_mod, xcd_map);
-    };
-    if (sel.stage != AST_PAINT_STAGE_ALL) {
-        // the single-pass overwrite paint in three parts, so that a caller can interleave tile rows with what consumes
-        // them (the slab pipeline: walk -> fold -> transform -> send, plane range by plane range)
+                                                              w.ovf, w.ovf_count, w.col_flags, dropped, closed_lo, closed_n, closed_mod);
+    }
+    // parts k .. k + span - 1 of K equal parts of the particle array, on whole grouping intervals: [first, second)
+    std::pair<size_t, size_t> part_bounds(int k, int span, int K) const {
+        const size_t pb = (size_t)((double)k / K * (double)np) / per_interval * per_interval;
+        const size_t pe = k + span == K ? np : (size_t)((double)(k + span) / K * (double)np) / per_interval * per_interval;
+        return {pb, pe};
+    }
+    // the scatter path's late list: deposits into buffer planes [x_lo, x_hi) with global atomics, if it holds fewer than n_below records
+    void late_global(unsigned wgs, int x_lo, int x_hi, unsigned long long n_below = ~0ull) {
+        late_deposit_kernel<T, W><<<wgs, 256, 0, s>>>((const T*)w.ovf, w.late, late_cap(), g, scale, grid, dropped, x_lo, x_hi, n_below);
+    }
+    // the overflow list's deposits into buffer planes [x_lo, x_hi) with global atomics
+    void overflow(unsigned wgs, int x_lo, int x_hi) {
+        AST_PROF("paint_tiled.overflow", s);
+        overflow_deposit_kernel<T, W><<<wgs, 256, 0, s>>>(pos, mass, w.ovf, w.ovf_count, g, scale, grid, dropped, x_lo, x_hi);
+    }
+
+    // ---- the paths ----
+    int two_pass_path() {
+        {
+            AST_PROF("paint_tiled.count", s);
+            index_pass<0>(pos, np, interval_grid(np), w.tile_count, nullptr, nullptr, nullptr, 0, nullptr, nullptr, dropped);
+        }
+        {
+            AST_PROF("paint_tiled.scan", s);
+            tile_scan();
+        }
+        {
+            AST_PROF("paint_tiled.fill", s);
+            index_pass<1>(pos, np, interval_grid(np), nullptr, w.tile_off, w.tile_fill, w.index, 0, nullptr, nullptr, nullptr);
+        }
+        deposit(w.tile_off, w.tile_count, 0);
+        return AST_OK;
+    }
+    int scattered_path() {
+        { const int rc = scatter_levels(); if (rc != AST_OK) return rc; }
+        deposit(nullptr, nullptr, 0);
+        AST_PROF("paint_tiled.overflow", s);
+        // The late list (records whose tile - or bucket - segment was full).  A few stragglers: global atomics.  A long list
+        // (clustered input without order in memory: a tenth of the particles, in a few hundred hot tiles) is a small paint
+        // of its own - counted per tile, scanned, its record numbers filled tile-major, then ONE workgroup per tile adds its
+        // records up in LDS and flushes the tile onto the grid: the two-pass variant with the list's records as particles.
+        // The list's length stays on the device: all kernels are launched, each looks at the count.
+        // (float32: any non-empty list.  Thousands of fp32 atomics on one blob cell, each rounded in arrival order, put it up
+        // to 7.6e-6 of the grid's maximum off the exact sum at 128^3 - beyond the 3e-6 the paint is held to; the LDS sums in
+        // double round once.  An empty list costs the same either way: every kernel reads the count and returns.)
+        const unsigned long long lds_min = hooks.late_lds_set ? hooks.late_lds_min : sizeof(T) == 4 ? 1ull : 262144ull;
+        late_global(1024, 0, g.nx_alloc, lds_min);
+        if (lds_min != ~0ull && late_cap() > 0) {
+            const T* list = (const T*)w.ovf;
+            const unsigned gl = interval_grid((size_t)late_cap(), 4096);
+            index_pass<0, 4>(list, (size_t)late_cap(), gl, w.tile_count, w.tile_off, w.tile_fill, w.late_index, 0, nullptr, nullptr, nullptr, w.late, lds_min);
+            tile_scan();
+            index_pass<1, 4>(list, (size_t)late_cap(), gl, w.tile_count, w.tile_off, w.tile_fill, w.late_index, 0, nullptr, nullptr, nullptr, w.late, lds_min);
+            tile_deposit_kernel<T, W, 4><<<ntiles < 8192u ? ntiles : 8192u, 256, 0, s>>>(list, nullptr, g, scale, w.late_index, w.tile_off,
+                                                                                       w.tile_count, 0, grid, dropped, ntiles);
+        }
+        return AST_OK;
+    }
+    // the accumulating single pass: fixed-capacity id segments, one workgroup per tile, global-atomic flush
+    int accumulate_path() {
+        {
+            AST_PROF("paint_tiled.fill", s);
+            index_pass<2>(pos, np, interval_grid(np), nullptr, nullptr, w.tile_fill, w.index, w.cap, w.ovf, w.ovf_count, dropped);
+        }
+        deposit(nullptr, w.tile_fill, w.cap);
+        overflow(1024, 0, g.nx_alloc);
+        return AST_OK;
+    }
+    int grouped_path() {
+        group(0, np, 0u, 0u);
+        deposit(nullptr, nullptr, 0);
+        overflow(1024, 0, g.nx_alloc);
+        return AST_OK;
+    }
+    // AST_PAINT_XSORTED: the particles come in ascending x (buffer planes).  They are grouped chunk by chunk
+    // (plan.chunk_planes planes' worth each); a tile row is walked as soon as the chunks cover its planes plus a
+    // margin - while the chunk's positions are still in the Infinity Cache, so the walk's gather does not go to
+    // HBM a second time.  A particle that arrives for a row already handed to the walk ("late": the input was not
+    // sorted after all) goes to the overflow list and is deposited with global atomics at the end - the result
+    // never depends on the assumption, only the speed.  A periodic grid's row 0 also takes the wrap of the LAST
+    // particles: it is walked last.  plan.streams == 2 (sp set): the walks run on a second stream, each beside the
+    // grouping of the following chunks (which wait for the walk before the one they overlap: the grouping must not run
+    // ahead, or the positions are gone from the cache before they are gathered).  last_walk: the event after the last walk.
+    int enqueue_chunks(SidePipe* sp, hipEvent_t& last_walk) {
+        const int K = plan.chunks;
+        const int m0 = g.nx_alloc == g.n ? 1 : 0;                  // rows [0, m0) are held back to the end
+        const uint32_t rs = (uint32_t)(g.nty * g.ntz);             // tiles per row
+        int prev = m0, nev = 0;
+        hipEvent_t walk_done[2] = {nullptr, nullptr};              // the last two walks on the side stream
+        for (int k = 0; k < K; ++k) {
+            const auto part = part_bounds(k, 1, K);
+            if (sp && walk_done[1]) AST_CHECK_HIP(hipStreamWaitEvent(s, walk_done[1], 0));
+            if (part.second > part.first) group(part.first, part.second, (uint32_t)m0 * rs, (uint32_t)(prev - m0) * rs);
+            // rows whose planes (plus the margin) the chunks 0..k cover
+            const int covered = (int)((long long)(k + 1) * g.nx_alloc / K) - plan.margin_planes;
+            const int r = k + 1 == K ? g.ntx : std::max(prev, std::min(g.ntx, covered / TX));
+            if (r > prev || k + 1 == K) {
+                const int rows = r - prev + (k + 1 == K ? m0 : 0);      // the last launch wraps around to row 0
+                hipStream_t ws = s;
+                if (sp) {
+                    AST_CHECK_HIP(hipEventRecord(sp->ev[nev], s));
+                    AST_CHECK_HIP(hipStreamWaitEvent(sp->side, sp->ev[nev], 0));
+                    ++nev;
+                    ws = sp->side;
+                }
+                if (rows > 0) walk(nullptr, nullptr, prev * g.nty, (unsigned)(rows * g.nty), ws);
+                if (sp) {
+                    AST_CHECK_HIP(hipEventRecord(sp->ev[nev], sp->side));
+                    walk_done[1] = walk_done[0];
+                    last_walk = walk_done[0] = sp->ev[nev];
+                    ++nev;
+                }
+                prev = r;
+            }
+        }
+        return AST_OK;
+    }
+    int xsorted_path() {
+        {   // (the pipeline's profile site and the side-stream lock end with this block, before the overflow deposit)
+            const bool two_streams = plan.streams > 1;
+            SidePipe* sp = two_streams ? side_pipe(2 * g.ntx + 4) : nullptr;
+            if (two_streams && !sp) { ast::set_error("ast_paint_tiled: no side stream"); return AST_ERR_HIP; }
+            AST_PROF("paint_tiled.pipeline", s);
+            // two host threads painting on one device share the side stream and its events: the pipeline is serialised
+            // per device; and whatever happens in the loop, `s` is joined with the side stream before this function
+            // returns - the caller may free or reuse the workspace on `s` right after
+            std::unique_lock<std::mutex> pipe_lock;
+            if (sp) pipe_lock = std::unique_lock<std::mutex>(sp->run);
+            hipEvent_t last_walk = nullptr;
+            const int rc = enqueue_chunks(sp, last_walk);
+            // an enqueue failed half way: whatever already runs on the side stream still reads the workspace
+            if (rc != AST_OK && sp) (void)hipStreamSynchronize(sp->side);
+            if (rc != AST_OK) return rc;
+            if (last_walk) AST_CHECK_HIP(hipStreamWaitEvent(s, last_walk, 0));
+            seams_and_fold();
+        }
+        overflow(1024, 0, g.nx_alloc);
+        return AST_OK;
+    }
+
+    // The single-pass overwrite paint in parts, so that a caller can interleave tile rows with what consumes them (the
+    // slab pipeline: walk -> fold -> transform -> send, plane range by plane range).  RESET has nothing left to do here.
+    int stage(const StageSel& sel) {
         if (two_pass || !overwrite || (flags & (AST_PAINT_DEFER_FOLD | AST_PAINT_XSORTED))) {
             ast::set_error("ast_paint_tiled_stage: needs AST_PAINT_OVERWRITE without TWO_PASS / DEFER_FOLD / XSORTED");
             return AST_ERR_ARG;
         }
-        if (sel.stage == AST_PAINT_STAGE_RESET) return AST_OK;                 // (the counters, above)
+        if (sel.stage == AST_PAINT_STAGE_RESET) return AST_OK;
         if (sel.stage == AST_PAINT_STAGE_GROUP) {
-            if (w.tpb) { const int rc = scatter_pass(); if (rc != AST_OK) return rc; }
-            else group_pass(0, np, 0u, 0u);
-            AST_CHECK_LAUNCH();
-            return AST_OK;
-        }
-        if (sel.stage == AST_PAINT_STAGE_GROUP_PART) {
-            // part row0 of nrows equal parts of the particle array (boundaries on whole grouping intervals, as in the
-            // x-sorted pipeline); tile rows [closed_row0, closed_row0 + closed_nrows) (mod ntx) have been walked already
+            if (w.tpb) { const int rc = scatter_levels(); if (rc != AST_OK) return rc; }
+            else group(0, np, 0u, 0u);
+        } else if (sel.stage == AST_PAINT_STAGE_GROUP_PART) {
+            // part row0 of nrows equal parts of the particle array; tile rows [closed_row0, closed_row0 + closed_nrows)
+            // (mod ntx) have been walked already
             // (nrows = parts | (span - 1) << 16: `span` CONSECUTIVE parts, row0 .. row0 + span - 1, in one launch - stages of
             // unequal size out of equal parts)
             const int k = sel.row0, K = sel.nrows & 0xffff, span = (sel.nrows >> 16) + 1;
@@ -2135,191 +2255,50 @@ int run_tiled(const T* pos, const T* mass, size_t np, TileGeom g, uint32_t ntile
                 ast::set_error("ast_paint_tiled_stage: GROUP_PART needs a slab buffer (not the scattered path), 0 <= part, part + span <= parts and closed rows inside the buffer");
                 return AST_ERR_ARG;
             }
-            const size_t pb = (size_t)((double)k / K * (double)np) / per_interval * per_interval;
-            const size_t pe = k + span == K ? np : (size_t)((double)(k + span) / K * (double)np) / per_interval * per_interval;
+            const auto part = part_bounds(k, span, K);
             const uint32_t rs = (uint32_t)(g.nty * g.ntz);             // tiles per row
-            if (pe > pb) group_pass(pb, pe, (uint32_t)sel.closed_row0 * rs, (uint32_t)sel.closed_nrows * rs, ntiles);
-            AST_CHECK_LAUNCH();
-            return AST_OK;
-        }
-        if (sel.row0 < 0 || sel.nrows < 1 || sel.row0 + sel.nrows > g.ntx) {
-            ast::set_error("ast_paint_tiled_stage: tile rows [%d, %d) outside [0, %d)", sel.row0, sel.row0 + sel.nrows, g.ntx);
-            return AST_ERR_ARG;
-        }
-        const int col0 = sel.row0 * g.nty;
-        const unsigned ncol = (unsigned)(sel.nrows * g.nty);
-        if (sel.stage == AST_PAINT_STAGE_WALK) {
-            walk_pass(nullptr, nullptr, col0, ncol, s);
-            if (plan.nseg > 1) {
-                AST_PROF("paint_tiled.seams", s);
-                z_seam_kernel<T, W><<<ncol, 256, 0, s>>>(w.zrec, g, scale, (uint32_t)std::min<unsigned long long>(5ull * w.cap, 0x3fffffffull),
-                                                          mass ? mass_bound : 1.0, grid, (T*)w.rec, offset, dropped, col0, plan.nseg);
-            }
-        } else if (sel.stage == AST_PAINT_STAGE_FOLD || sel.stage == AST_PAINT_STAGE_LATE) {
-            if (sel.stage == AST_PAINT_STAGE_FOLD) {
-                AST_PROF("paint_tiled.fold", s);
-                column_fold_kernel<T, W><<<ncol, 256, 0, s>>>((const T*)w.rec, g, grid, col0);
-            }
-            // the overflow / late list's deposits into these rows' planes (the lists are complete after the GROUP stage)
-            AST_PROF("paint_tiled.overflow", s);
-            const int x_lo = sel.row0 * TX, x_hi = std::min(g.nx_alloc, (sel.row0 + sel.nrows) * TX);
-            if (w.tpb)
-                late_deposit_kernel<T, W><<<128, 256, 0, s>>>((const T*)w.ovf, w.late, late_capacity(np, sizeof(T)), g, scale, grid, dropped, x_lo, x_hi);
-            else
-                overflow_deposit_kernel<T, W><<<128, 256, 0, s>>>(pos, mass, w.ovf, w.ovf_count, g, scale, grid, dropped, x_lo, x_hi);
+            if (part.second > part.first) group(part.first, part.second, (uint32_t)sel.closed_row0 * rs, (uint32_t)sel.closed_nrows * rs, ntiles);
         } else {
-            ast::set_error("ast_paint_tiled_stage: unknown stage %d", sel.stage);
-            return AST_ERR_ARG;
+            if (sel.row0 < 0 || sel.nrows < 1 || sel.row0 + sel.nrows > g.ntx) {
+                ast::set_error("ast_paint_tiled_stage: tile rows [%d, %d) outside [0, %d)", sel.row0, sel.row0 + sel.nrows, g.ntx);
+                return AST_ERR_ARG;
+            }
+            const int col0 = sel.row0 * g.nty;
+            const unsigned ncol = (unsigned)(sel.nrows * g.nty);
+            if (sel.stage == AST_PAINT_STAGE_WALK) {
+                walk(nullptr, nullptr, col0, ncol, s);
+                seams(col0, ncol);
+            } else if (sel.stage == AST_PAINT_STAGE_FOLD || sel.stage == AST_PAINT_STAGE_LATE) {
+                if (sel.stage == AST_PAINT_STAGE_FOLD) fold(col0, ncol);
+                // the overflow / late list's deposits into these rows' planes (the lists are complete after the GROUP stage)
+                const int x_lo = sel.row0 * TX, x_hi = std::min(g.nx_alloc, (sel.row0 + sel.nrows) * TX);
+                if (w.tpb) {
+                    AST_PROF("paint_tiled.overflow", s);
+                    late_global(128, x_lo, x_hi);
+                } else {
+                    overflow(128, x_lo, x_hi);
+                }
+            } else {
+                ast::set_error("ast_paint_tiled_stage: unknown stage %d", sel.stage);
+                return AST_ERR_ARG;
+            }
         }
         AST_CHECK_LAUNCH();
         return AST_OK;
     }
-    if (two_pass) {
-        {
-            AST_PROF("paint_tiled.count", s);
-            index_pass(std::integral_constant<int, 0>{}, w.tile_count, nullptr, nullptr, nullptr, 0, nullptr, nullptr, dropped);
-        }
-        const uint32_t nblk = (ntiles + 1023) / 1024;
-        {
-            AST_PROF("paint_tiled.scan", s);
-            scan_blocks_kernel<<<nblk, 256, 0, s>>>(w.tile_count, w.tile_off, w.block_sums, ntiles);
-            scan_sums_kernel<<<1, 256, 0, s>>>(w.block_sums, nblk);
-            scan_add_kernel<<<nblk, 256, 0, s>>>(w.tile_off, w.block_sums, ntiles);
-        }
-        {
-            AST_PROF("paint_tiled.fill", s);
-            index_pass(std::integral_constant<int, 1>{}, nullptr, w.tile_off, w.tile_fill, w.index, 0, nullptr, nullptr, nullptr);
-        }
-        deposit_pass(w.tile_off, w.tile_count, 0);
-    } else if (overwrite && w.tpb) {
-        { const int rc = scatter_pass(); if (rc != AST_OK) return rc; }
-        deposit_pass(nullptr, nullptr, 0);
-        AST_PROF("paint_tiled.overflow", s);
-        // The late list (records whose tile - or bucket - segment was full).  A few stragglers: global atomics.  A long list
-        // (clustered input without order in memory: a tenth of the particles, in a few hundred hot tiles) is a small paint
-        // of its own - counted per tile, scanned, its record numbers filled tile-major, then ONE workgroup per tile adds its
-        // records up in LDS and flushes the tile onto the grid: the two-pass variant with the list's records as particles.
-        // The list's length stays on the device: all kernels are launched, each looks at the count.
-        const unsigned long long late_cap = late_capacity(np, sizeof(T));
-        // (float32: any non-empty list.  Thousands of fp32 atomics on one blob cell, each rounded in arrival order, put it up
-        // to 7.6e-6 of the grid's maximum off the exact sum at 128^3 - beyond the 3e-6 the paint is held to; the LDS sums in
-        // double round once.  An empty list costs the same either way: every kernel reads the count and returns.)
-        const unsigned long long lds_min = getenv("AST_PAINT_LATE_LDS_MIN") ? strtoull(getenv("AST_PAINT_LATE_LDS_MIN"), nullptr, 10)
-                                                                            : sizeof(T) == 4 ? 1ull : 262144ull;
-        late_deposit_kernel<T, W><<<1024, 256, 0, s>>>((const T*)w.ovf, w.late, late_cap, g, scale, grid, dropped, 0, g.nx_alloc, lds_min);
-        if (lds_min != ~0ull && late_cap > 0) {
-            const size_t lint = (late_cap + per_interval - 1) / per_interval;
-            const unsigned gl = (unsigned)(lint > 4096 ? 4096 : lint);
-            const uint32_t nblk = (ntiles + 1023) / 1024;
-            auto late_index_pass = [&](auto mode) {
-                constexpr int MODE = decltype(mode)::value;
-                if (plainx)
-                    tile_index_kernel<T, W, MODE, true, 4><<<gl, 256, 0, s>>>((const T*)w.ovf, (size_t)late_cap, g, w.tile_count, w.tile_off, w.tile_fill,
-                                                                              w.late_index, 0, nullptr, nullptr, w.col_flags, nullptr, w.late, lds_min);
-                else
-                    tile_index_kernel<T, W, MODE, false, 4><<<gl, 256, 0, s>>>((const T*)w.ovf, (size_t)late_cap, g, w.tile_count, w.tile_off, w.tile_fill,
-                                                                               w.late_index, 0, nullptr, nullptr, w.col_flags, nullptr, w.late, lds_min);
-            };
-            late_index_pass(std::integral_constant<int, 0>{});
-            scan_blocks_kernel<<<nblk, 256, 0, s>>>(w.tile_count, w.tile_off, w.block_sums, ntiles);
-            scan_sums_kernel<<<1, 256, 0, s>>>(w.block_sums, nblk);
-            scan_add_kernel<<<nblk, 256, 0, s>>>(w.tile_off, w.block_sums, ntiles);
-            late_index_pass(std::integral_constant<int, 1>{});
-            tile_deposit_kernel<T, W, 4><<<ntiles < 8192u ? ntiles : 8192u, 256, 0, s>>>((const T*)w.ovf, nullptr, g, scale, w.late_index, w.tile_off,
-                                                                                       w.tile_count, 0, grid, dropped, ntiles);
-        }
-    } else if (overwrite) {
-        // AST_PAINT_XSORTED: the particles come in ascending x (buffer planes).  They are grouped chunk by chunk
-        // (plan.chunk_planes planes' worth each); a tile row is walked as soon as the chunks cover its planes plus a
-        // margin - while the chunk's positions are still in the Infinity Cache, so the walk's gather does not go to
-        // HBM a second time.  A particle that arrives for a row already handed to the walk ("late": the input was not
-        // sorted after all) goes to the overflow list and is deposited with global atomics at the end - the result
-        // never depends on the assumption, only the speed.  A periodic grid's row 0 also takes the wrap of the LAST
-        // particles: it is walked last.  plan.streams == 2: the walks run on a second stream, each beside the grouping
-        // of the following chunks (which wait for the walk before the one they overlap: the grouping must not run
-        // ahead, or the positions are gone from the cache before they are gathered).
-        const int K = plan.chunks;
-        if (K == 1) {
-            group_pass(0, np, 0u, 0u);
-            deposit_pass(nullptr, nullptr, 0);
-        } else {
-            const bool two_streams = plan.streams > 1;
-            SidePipe* sp = two_streams ? side_pipe(2 * g.ntx + 4) : nullptr;
-            if (two_streams && !sp) { ast::set_error("ast_paint_tiled: no side stream"); return AST_ERR_HIP; }
-            AST_PROF("paint_tiled.pipeline", s);
-            // two host threads painting on one device share the side stream and its events: the pipeline is serialised
-            // per device; and whatever happens in the loop, `s` is joined with the side stream before this
-            // function returns - the caller may free or reuse the workspace on `s` right after
-            std::unique_lock<std::mutex> pipe_lock;
-            if (two_streams) pipe_lock = std::unique_lock<std::mutex>(sp->run);
-            const bool x_periodic = g.nx_alloc == g.n;
-            const int m0 = x_periodic ? 1 : 0;                         // rows [0, m0) are held back to the end
-            const uint32_t rs = (uint32_t)(g.nty * g.ntz);             // tiles per row
-            int prev = m0, nev = 0;
-            hipEvent_t walk_done[2] = {nullptr, nullptr};              // the last two walks on the side stream
-            auto chunk_loop = [&]() -> int {
-            for (int k = 0; k < K; ++k) {
-                const size_t pb = (size_t)((double)k / K * (double)np) / per_interval * per_interval;
-                const size_t pe = k + 1 == K ? np : (size_t)((double)(k + 1) / K * (double)np) / per_interval * per_interval;
-                if (two_streams && walk_done[1]) AST_CHECK_HIP(hipStreamWaitEvent(s, walk_done[1], 0));
-                if (pe > pb) group_pass(pb, pe, (uint32_t)m0 * rs, (uint32_t)(prev - m0) * rs);
-                // rows whose planes (plus the margin) the chunks 0..k cover
-                const int covered = (int)((long long)(k + 1) * g.nx_alloc / K) - plan.margin_planes;
-                const int r = k + 1 == K ? g.ntx : std::max(prev, std::min(g.ntx, covered / TX));
-                if (r > prev || k + 1 == K) {
-                    const int rows = r - prev + (k + 1 == K ? m0 : 0);      // the last launch wraps around to row 0
-                    hipStream_t ws = s;
-                    if (two_streams) {
-                        AST_CHECK_HIP(hipEventRecord(sp->ev[nev], s));
-                        AST_CHECK_HIP(hipStreamWaitEvent(sp->side, sp->ev[nev], 0));
-                        ++nev;
-                        ws = sp->side;
-                    }
-                    if (rows > 0) walk_pass(nullptr, nullptr, prev * g.nty, (unsigned)(rows * g.nty), ws);
-                    if (two_streams) {
-                        AST_CHECK_HIP(hipEventRecord(sp->ev[nev], sp->side));
-                        walk_done[1] = walk_done[0];
-                        walk_done[0] = sp->ev[nev];
-                        ++nev;
-                    }
-                    prev = r;
-                }
-            }
-            return AST_OK;
-            };
-            const int loop_rc = chunk_loop();
-            if (two_streams) {
-                if (loop_rc != AST_OK) {
-                    // an enqueue failed half way: whatever already runs on the side stream still reads the workspace
-                    (void)hipStreamSynchronize(sp->side);
-                    return loop_rc;
-                }
-                if (walk_done[0]) AST_CHECK_HIP(hipStreamWaitEvent(s, walk_done[0], 0));
-            } else if (loop_rc != AST_OK) {
-                return loop_rc;
-            }
-            fold_pass();
-        }
-        AST_PROF("paint_tiled.overflow", s);
-        overflow_deposit_kernel<T, W><<<1024, 256, 0, s>>>(pos, mass, w.ovf, w.ovf_count, g, scale, grid, dropped, 0, g.nx_alloc);
-    } else {
-        {
-            AST_PROF("paint_tiled.fill", s);
-            index_pass(std::integral_constant<int, 2>{}, nullptr, nullptr, w.tile_fill, w.index, w.cap, w.ovf, w.ovf_count, dropped);
-        }
-        deposit_pass(nullptr, w.tile_fill, w.cap);
-#ifdef PAINT_WALK_TEST
-        {
-            AST_PROF("paint_tiled.walktest", s);
-            walk_test_kernel<T><<<ncols, 256, 0, s>>>(pos, g, w.index, w.tile_fill, w.cap, (T*)w.rec);
-        }
-#endif
-        AST_PROF("paint_tiled.overflow", s);
-        overflow_deposit_kernel<T, W><<<1024, 256, 0, s>>>(pos, mass, w.ovf, w.ovf_count, g, scale, grid, dropped, 0, g.nx_alloc);
+
+    int run(const StageSel& sel) {
+        // ovf_count, col_flags, tile_count, tile_fill, fill64 and the scatter path's counters are contiguous at the front of the workspace
+        if (sel.stage == AST_PAINT_STAGE_ALL || sel.stage == AST_PAINT_STAGE_GROUP || sel.stage == AST_PAINT_STAGE_RESET)
+            AST_CHECK_HIP(hipMemsetAsync(w.ovf_count, 0, (size_t)((char*)w.tile_off - (char*)w.ovf_count), s));
+        if (sel.stage != AST_PAINT_STAGE_ALL) return stage(sel);
+        const int rc = two_pass ? two_pass_path() : !overwrite ? accumulate_path() : w.tpb ? scattered_path()
+                     : plan.chunks > 1 ? xsorted_path() : grouped_path();
+        if (rc != AST_OK) return rc;
+        AST_CHECK_LAUNCH();
+        return AST_OK;
     }
-    AST_CHECK_LAUNCH();
-    return AST_OK;
-}
+};
 
 }  // namespace
 
@@ -2341,11 +2320,8 @@ extern "C" size_t ast_paint_scatter_late_capacity(int dtype, size_t np) {
 
 extern "C" size_t ast_paint_tiled_workspace_bytes(int window, int dtype, size_t np, int nmesh, int nx_alloc, int flags) {
     TileGeom g;
-    uint32_t ntiles = 0;
-    if (nmesh <= 0 || nx_alloc <= 0 || !tiled_geometry(nmesh, nx_alloc, g, ntiles)) return 0;
-    return carve(nullptr, np, ntiles, (uint32_t)(g.ntx * g.nty), flags, dtype == AST_F32 ? 4 : 8,
-                 record_bytes(window, g, dtype == AST_F32 ? 4 : 8, flags),
-                 seam_bytes(window, g, np, dtype == AST_F32 ? 4 : 8, flags)).bytes;
+    if (nmesh <= 0 || nx_alloc <= 0 || !tiled_geometry(nmesh, nx_alloc, g)) return 0;
+    return paint_layout(nullptr, window, dtype == AST_F32 ? 4 : 8, np, g, flags, read_test_hooks()).bytes;
 }
 
 // Where ast_paint_tiled(... AST_PAINT_OVERWRITE | AST_PAINT_DEFER_FOLD) left the halo records of a paint with
@@ -2355,10 +2331,8 @@ extern "C" int ast_paint_tiled_halo(void* workspace, int window, int dtype, size
     AST_CHECK_ARG(workspace && rec_out && (flags & AST_PAINT_OVERWRITE));
     AST_CHECK_ARG(window == AST_WIN_CIC || window == AST_WIN_TSC);
     TileGeom g;
-    uint32_t ntiles = 0;
-    AST_CHECK_ARG(nmesh > 0 && nx_alloc > 0 && tiled_geometry(nmesh, nx_alloc, g, ntiles));
-    const size_t esz = dtype == AST_F32 ? 4 : 8;
-    *rec_out = carve(workspace, np, ntiles, (uint32_t)(g.ntx * g.nty), flags, esz, record_bytes(window, g, esz, flags)).rec;
+    AST_CHECK_ARG(nmesh > 0 && nx_alloc > 0 && tiled_geometry(nmesh, nx_alloc, g));
+    *rec_out = paint_layout(workspace, window, dtype == AST_F32 ? 4 : 8, np, g, flags, read_test_hooks()).rec;
     return AST_OK;
 }
 
@@ -2384,13 +2358,11 @@ extern "C" int ast_paint_tiled_list_stats(void* workspace, int window, int dtype
                                           int flags, unsigned long long* out, void* stream) {
     AST_CHECK_ARG(workspace && out && (flags & AST_PAINT_OVERWRITE) && !(flags & AST_PAINT_TWO_PASS));
     TileGeom g;
-    uint32_t ntiles = 0;
-    AST_CHECK_ARG(nmesh > 0 && nx_alloc > 0 && tiled_geometry(nmesh, nx_alloc, g, ntiles));
-    const size_t esz = dtype == AST_F32 ? 4 : 8;
-    const Workspace w = carve(workspace, np, ntiles, (uint32_t)(g.ntx * g.nty), flags, esz, record_bytes(window, g, esz, flags));
+    AST_CHECK_ARG(nmesh > 0 && nx_alloc > 0 && tiled_geometry(nmesh, nx_alloc, g));
+    const Workspace w = paint_layout(workspace, window, dtype == AST_F32 ? 4 : 8, np, g, flags, read_test_hooks());
     hipStream_t s = ast::as_stream(stream);
     AST_CHECK_HIP(hipMemsetAsync(out, 0, 4 * sizeof(unsigned long long), s));
-    list_stats_kernel<<<256, 256, 0, s>>>(w.fill64, ntiles, w.rcap, w.scap, w.tpb ? w.late : w.ovf_count, out);
+    list_stats_kernel<<<256, 256, 0, s>>>(w.fill64, w.ntiles, w.rcap, w.scap, w.tpb ? w.late : w.ovf_count, out);
     AST_CHECK_LAUNCH();
     return AST_OK;
 }
@@ -2530,6 +2502,15 @@ extern "C" int ast_paint_occupancy_probe(const void* pos, int dtype, size_t np, 
     return AST_OK;
 }
 
+namespace {
+// Explicit instantiations, here behind the probes' kernels: the members are instantiated in the order of their declarations, and the kernels reach the code
+// object in the order the members first launch them - whatever the call graph of the host code looks like.
+template struct TiledPaint<float, 2>;
+template struct TiledPaint<float, 3>;
+template struct TiledPaint<double, 2>;
+template struct TiledPaint<double, 3>;
+}  // namespace
+
 static int paint_tiled_impl(int window, int dtype, const void* pos, const void* mass, size_t np, int nmesh,
                             double boxsize, double scale, int x_start, int nx_alloc, void* grid,
                             void* workspace, size_t workspace_bytes, unsigned long long* dropped,
@@ -2553,8 +2534,7 @@ static int paint_tiled_impl(int window, int dtype, const void* pos, const void* 
     AST_CHECK_ARG(offset == 0.0 || (flags & AST_PAINT_OVERWRITE));
     AST_CHECK_ARG(offset_start >= 0 && offset_start <= nx_alloc && (offset_count < 0 || offset_start + offset_count <= nx_alloc));
     TileGeom g;
-    uint32_t ntiles = 0;
-    if (!tiled_geometry(nmesh, nx_alloc, g, ntiles)) {
+    if (!tiled_geometry(nmesh, nx_alloc, g)) {
         ast::set_error("ast_paint_tiled: nmesh must be a multiple of %d", TZ);
         return AST_ERR_ARG;
     }
@@ -2563,22 +2543,22 @@ static int paint_tiled_impl(int window, int dtype, const void* pos, const void* 
     g.shift = shift_cells;
     g.off_lo = offset_start;
     g.off_hi = offset_start + (offset_count < 0 ? nx_alloc : offset_count);
-    const size_t need = carve(nullptr, np, ntiles, (uint32_t)(g.ntx * g.nty), flags, dtype == AST_F32 ? 4 : 8,
-                              record_bytes(window, g, dtype == AST_F32 ? 4 : 8, flags),
-                              seam_bytes(window, g, np, dtype == AST_F32 ? 4 : 8, flags)).bytes;
-    if (workspace_bytes < need) {
-        ast::set_error("ast_paint_tiled: workspace too small (%zu < %zu bytes)", workspace_bytes, need);
+    const TestHooks hooks = read_test_hooks();
+    const Workspace w = paint_layout(workspace, window, dtype == AST_F32 ? 4 : 8, np, g, flags, hooks);
+    if (workspace_bytes < w.bytes) {
+        ast::set_error("ast_paint_tiled: workspace too small (%zu < %zu bytes)", workspace_bytes, w.bytes);
         return AST_ERR_WORKSPACE;
     }
-    hipStream_t s = ast::as_stream(stream);
-    if (dtype == AST_F32) {
-        if (window == AST_WIN_CIC)
-            return run_tiled<float, 2>((const float*)pos, (const float*)mass, np, g, ntiles, scale, (float*)grid, workspace, dropped, flags, mass_bound, offset, s, sel);
-        return run_tiled<float, 3>((const float*)pos, (const float*)mass, np, g, ntiles, scale, (float*)grid, workspace, dropped, flags, mass_bound, offset, s, sel);
-    }
-    if (window == AST_WIN_CIC)
-        return run_tiled<double, 2>((const double*)pos, (const double*)mass, np, g, ntiles, scale, (double*)grid, workspace, dropped, flags, mass_bound, offset, s, sel);
-    return run_tiled<double, 3>((const double*)pos, (const double*)mass, np, g, ntiles, scale, (double*)grid, workspace, dropped, flags, mass_bound, offset, s, sel);
+    auto run = [&](auto zero, auto window_width) {
+        using T = decltype(zero);
+        TiledPaint<T, decltype(window_width)::value> paint{(const T*)pos, (const T*)mass, np, g, scale, (T*)grid, dropped, flags,
+                                                            mass_bound, offset, ast::as_stream(stream), hooks, w};
+        return paint.run(sel);
+    };
+    using W2 = std::integral_constant<int, 2>;
+    using W3 = std::integral_constant<int, 3>;
+    if (dtype == AST_F32) return window == AST_WIN_CIC ? run(0.0f, W2{}) : run(0.0f, W3{});
+    return window == AST_WIN_CIC ? run(0.0, W2{}) : run(0.0, W3{});
 }
 
 extern "C" int ast_paint_tiled(int window, int dtype, const void* pos, const void* mass, size_t np, int nmesh,

@@ -14,11 +14,8 @@ constexpr int TX = TILE_TX, TY = TILE_TY, TZ = TILE_TZ;   // owned cells per til
 
 // Pitch (elements) of a halo-record z line: n.  (Every line then starts at a multiple of 4 KB for fp32 and n = 1024, like
 // the tile segments of the paint workspace before their strides were skewed - but here a pitch of n + 32 measured no
-// better: step 12.79 / 12.86 against 12.73 / 12.81 ms, scripts/micro/ab_rec_skew.sh.  -DREC_LINE_SKEW=32 for A/B builds.)
-#ifndef REC_LINE_SKEW
-#define REC_LINE_SKEW 0
-#endif
-__host__ __device__ inline size_t rec_pitch(size_t n) { return n + REC_LINE_SKEW; }
+// better: step 12.79 / 12.86 against 12.73 / 12.81 ms.)
+__host__ __device__ inline size_t rec_pitch(size_t n) { return n; }
 
 // halo ring of one (LX x LY) plane of the LDS tile: the cells a column deposits for its x / y
 // neighbours, kept as z lines of the column's halo record [column][ring cell][z]
