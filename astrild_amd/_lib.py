@@ -21,6 +21,9 @@ BIN = {"integer": 0, "float64": 1}      # AST_BIN_*
 PAINT_TWO_PASS, PAINT_OVERWRITE, PAINT_DEFER_FOLD, PAINT_SCATTERED, PAINT_XSORTED = 1, 2, 4, 8, 16
 PAINT_STAGE_ALL, PAINT_STAGE_GROUP, PAINT_STAGE_WALK, PAINT_STAGE_FOLD = -1, 0, 1, 2
 PAINT_STAGE_GROUP_PART, PAINT_STAGE_RESET, PAINT_STAGE_LATE = 3, 4, 5
+PVPDF_KIND = {"z_sign": 0, "radial": 1}     # AST_PVPDF_*
+PVPDF_MAX_BINS = 1 << 22                    # ast_pairwise_pdf_max_bins(), known here so that arguments are checked
+PVPDF_MAX_MOMENT_ROWS = 480                 # without a library call (AST_PVPDF_MAX_MOMENT_ROWS)
 
 
 class AstrildHipError(RuntimeError):
@@ -156,6 +159,11 @@ SIGNATURES = {
     "ast_pairwise_max_bins": (_i, []),
     "ast_pairwise_tv_prepare": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _sz, _vp, _sz, _vp]),
     "ast_pairwise_tv": (_i, [_vp, _sz, _sz, _i, _d, _i, _vp, _vp, _vp, _vp]),
+    "ast_pairwise_pdf_workspace_bytes": (_sz, [_sz, _i, _i, _i]),
+    "ast_pairwise_pdf_max_bins": (_i, []),
+    "ast_pairwise_pdf_lds_bins": (_i, [_i, _i]),
+    "ast_pairwise_pdf_prepare": (_i, [_vp, _i, _vp, _i, _sz, _vp, _sz, _vp]),
+    "ast_pairwise_pdf": (_i, [_vp, _sz, _sz, _i, _d, _i, _i, _d, _d, _sz, _sz, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ast_tpcf_workspace_bytes": (_sz, [_sz, _i, _i]),
     "ast_tpcf_max_bins": (_i, []),
     "ast_tpcf_prepare": (_i, [_vp, _i, _vp, _i, _i, _d, _sz, _vp, _sz, _vp, _vp]),

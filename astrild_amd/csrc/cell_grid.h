@@ -1,7 +1,9 @@
-// Uniform cell grid shared by the pair finders (pairwise.hip, tpcf.hip): objects sorted by cell with a counting sort
-// (a per-file count kernel -> grid_scan_kernel -> grid_scatter_kernel), and a work list of (tile of BLOCK objects of a
-// cell, one of the GRID_NEIGH half-shell neighbours) that a persistent pair kernel walks.  Everything here has internal
-// linkage: each translation unit gets its own copy of the kernels and of the offset table.
+// Uniform cell grid shared by the pair finders (pairwise.hip, pairwise_pdf.hip, tpcf.hip): objects sorted by cell with a
+// counting sort (a count kernel -> grid_scan_kernel -> grid_scatter_kernel), and a work list of (tile of BLOCK objects of
+// a cell, one of the GRID_NEIGH half-shell neighbours) that a persistent pair kernel walks.  The grid_box_* part is the
+// non-periodic grid over the catalogue's bounding box (pairwise.hip, pairwise_pdf.hip); tpcf.hip plans its own periodic
+// one.  Everything here has internal linkage: each translation unit gets its own copy of the kernels and of the offset
+// table.
 #pragma once
 #include "ast_common.h"
 
@@ -98,6 +100,82 @@ __device__ inline double wave_min(double v) {
 __device__ inline double wave_max(double v) {
     for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
     return v;
+}
+
+// ---- the non-periodic grid over a bounding box; Obj needs `double r[3]`
+constexpr size_t GRID_BOX_MAX_CELLS = size_t(1) << 20;
+
+struct GridBoxParams {
+    unsigned long long kmin[3], kmax[3];    // bounding box as order-preserving keys (atomicMin / atomicMax)
+    double lo[3], inv_cs[3];
+    int dims[3];
+    unsigned ncells, ntiles;
+};
+
+inline size_t grid_box_cells_cap(size_t n) { return n < 1 ? 1 : (n < GRID_BOX_MAX_CELLS ? n : GRID_BOX_MAX_CELLS); }
+
+// One thread: the grid.  Cells are at least s = rmax (1 + 1e-6) wide per axis, plus a margin for the rounding
+// of coordinates far from the origin, so a pair within reach lies in the same or an adjacent cell; at most `cap`
+// cells in all (wider cells past that).  single != 0: one cell.  (A template so that only the files that launch it
+// carry a copy.)
+template <typename Params>
+__global__ void grid_box_plan_kernel(Params* prm, double rmax, unsigned cap, int single) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    double lo[3], ext[3], amax = 0.0;
+    for (int a = 0; a < 3; ++a) {
+        lo[a] = key2d(prm->kmin[a]);
+        const double hi = key2d(prm->kmax[a]);
+        ext[a] = hi - lo[a];
+        amax = fmax(amax, fmax(fabs(lo[a]), fabs(hi)));
+    }
+    int dims[3] = {1, 1, 1};
+    if (!single) {
+        double s = rmax * (1.0 + 1e-6) + amax * 1e-12;
+        for (;;) {
+            double prod = 1.0;
+            for (int a = 0; a < 3; ++a) {
+                double m = floor(ext[a] / s);
+                if (!(m >= 1.0)) m = 1.0;
+                if (m > (double)GRID_BOX_MAX_CELLS) m = (double)GRID_BOX_MAX_CELLS;
+                dims[a] = (int)m;
+                prod *= m;
+            }
+            if (prod <= (double)cap) break;
+            s *= 1.25;
+        }
+    }
+    for (int a = 0; a < 3; ++a) {
+        prm->lo[a] = lo[a];
+        prm->dims[a] = dims[a];
+        prm->inv_cs[a] = dims[a] > 1 ? (double)dims[a] / ext[a] : 0.0;
+    }
+    prm->ncells = (unsigned)dims[0] * (unsigned)dims[1] * (unsigned)dims[2];
+}
+
+template <typename Obj>
+__device__ inline unsigned grid_box_cell(const Obj& o, const GridBoxParams& p) {
+    int c[3];
+    for (int a = 0; a < 3; ++a) {
+        double v = (o.r[a] - p.lo[a]) * p.inv_cs[a];
+        const double top = (double)(p.dims[a] - 1);
+        if (!(v >= 0.0)) v = 0.0;
+        if (v > top) v = top;
+        c[a] = (int)v;
+    }
+    return ((unsigned)c[2] * (unsigned)p.dims[1] + (unsigned)c[1]) * (unsigned)p.dims[0] + (unsigned)c[0];
+}
+
+template <typename Obj>
+__global__ void __launch_bounds__(256)
+grid_box_count_kernel(const Obj* __restrict__ obj, size_t n, const GridBoxParams* prm, unsigned* __restrict__ cell_of,
+                      unsigned* __restrict__ cnt) {
+    const GridBoxParams p = *prm;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const unsigned c = grid_box_cell(obj[i], p);
+        cell_of[i] = c;
+        atomicAdd(&cnt[c], 1u);
+    }
 }
 
 }  // namespace

@@ -11,19 +11,13 @@ namespace {
 constexpr int PV_BLOCK = 256;               // i objects per tile = j objects per LDS stage
 constexpr int PV_WAVES = PV_BLOCK / 64;
 constexpr int PV_GRID = 1024;               // persistent pair-kernel workgroups (256 CUs x 4)
-constexpr size_t PV_MAX_CELLS = size_t(1) << 20;
 constexpr int PV_MAX_BINS = 480;            // 4 wave histograms x 24 B x bins + the j stage fit 64 KiB of LDS
 
 struct PvObj { double r[3], u[3], t[3]; };
 
-struct PvParams {
-    unsigned long long kmin[3], kmax[3];    // bounding box as order-preserving keys (atomicMin / atomicMax)
-    double lo[3], inv_cs[3];
-    int dims[3];
-    unsigned ncells, ntiles;
-};
+using PvParams = GridBoxParams;
 
-inline size_t cells_cap(size_t n) { return n < 1 ? 1 : (n < PV_MAX_CELLS ? n : PV_MAX_CELLS); }
+inline size_t cells_cap(size_t n) { return grid_box_cells_cap(n); }
 
 struct PvLayout {
     size_t params, cnt, cell_start, tile_start, cursor, cell_of, obj, sorted, part, total;
@@ -99,66 +93,6 @@ pv_prep_kernel(const TP* __restrict__ pos, const TV* __restrict__ vel, int vel_n
             atomicMin(&prm->kmin[a], d2key(mn));
             atomicMax(&prm->kmax[a], d2key(mx));
         }
-    }
-}
-
-// One thread: the grid.  Cells are at least `target` = rmax (1 + 1e-6) wide per axis (plus a margin for the rounding
-// of coordinates far from the origin), so a pair within reach lies in the same or an adjacent cell; at most `cap`
-// cells in all (wider cells past that).  single != 0: one cell (ASTRILD_PV_CELLS=0).
-__global__ void pv_plan_kernel(PvParams* prm, double rmax, unsigned cap, int single) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    double lo[3], ext[3], amax = 0.0;
-    for (int a = 0; a < 3; ++a) {
-        lo[a] = key2d(prm->kmin[a]);
-        const double hi = key2d(prm->kmax[a]);
-        ext[a] = hi - lo[a];
-        amax = fmax(amax, fmax(fabs(lo[a]), fabs(hi)));
-    }
-    int dims[3] = {1, 1, 1};
-    if (!single) {
-        double s = rmax * (1.0 + 1e-6) + amax * 1e-12;
-        for (;;) {
-            double prod = 1.0;
-            for (int a = 0; a < 3; ++a) {
-                double m = floor(ext[a] / s);
-                if (!(m >= 1.0)) m = 1.0;
-                if (m > (double)PV_MAX_CELLS) m = (double)PV_MAX_CELLS;
-                dims[a] = (int)m;
-                prod *= m;
-            }
-            if (prod <= (double)cap) break;
-            s *= 1.25;
-        }
-    }
-    for (int a = 0; a < 3; ++a) {
-        prm->lo[a] = lo[a];
-        prm->dims[a] = dims[a];
-        prm->inv_cs[a] = dims[a] > 1 ? (double)dims[a] / ext[a] : 0.0;
-    }
-    prm->ncells = (unsigned)dims[0] * (unsigned)dims[1] * (unsigned)dims[2];
-}
-
-__device__ inline unsigned pv_cell(const PvObj& o, const PvParams& p) {
-    int c[3];
-    for (int a = 0; a < 3; ++a) {
-        double v = (o.r[a] - p.lo[a]) * p.inv_cs[a];
-        const double top = (double)(p.dims[a] - 1);
-        if (!(v >= 0.0)) v = 0.0;
-        if (v > top) v = top;
-        c[a] = (int)v;
-    }
-    return ((unsigned)c[2] * (unsigned)p.dims[1] + (unsigned)c[1]) * (unsigned)p.dims[0] + (unsigned)c[0];
-}
-
-__global__ void __launch_bounds__(256)
-pv_count_kernel(const PvObj* __restrict__ obj, size_t n, const PvParams* prm, unsigned* __restrict__ cell_of,
-                unsigned* __restrict__ cnt) {
-    const PvParams p = *prm;
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const unsigned c = pv_cell(obj[i], p);
-        cell_of[i] = c;
-        atomicAdd(&cnt[c], 1u);
     }
 }
 
@@ -352,10 +286,10 @@ extern "C" int ast_pairwise_tv(void* work_d, size_t work_bytes, size_t n, int bi
     const double rmax = (double)binnr * binwidth;
     {
         AST_PROF("pairwise_grid", s);
-        pv_plan_kernel<<<1, 64, 0, s>>>(prm, rmax, (unsigned)cap, single_cell);
+        grid_box_plan_kernel<<<1, 64, 0, s>>>(prm, rmax, (unsigned)cap, single_cell);
         AST_CHECK_LAUNCH();
         AST_CHECK_HIP(hipMemsetAsync(cnt, 0, cap * 4, s));
-        pv_count_kernel<<<ast::stream_grid(n, 256), 256, 0, s>>>(obj, n, prm, cell_of, cnt);
+        grid_box_count_kernel<<<ast::stream_grid(n, 256), 256, 0, s>>>(obj, n, prm, cell_of, cnt);
         AST_CHECK_LAUNCH();
         grid_scan_kernel<PV_BLOCK><<<1, 1024, 0, s>>>(cnt, prm, cell_start, tile_start, cursor);
         AST_CHECK_LAUNCH();

@@ -1224,6 +1224,91 @@ def pairwise_tv(pos, vel_cart_or_ang, binnr, binwidth, theta1=None, theta2=None)
     return nom, denom, counts
 
 
+# ------------------------------------------------------------------ pairwise-velocity histograms
+def check_pairwise_pdf_args(pos_shape, vel_shape, r, dist_bin, vel_bin, kind, dist_width, vel_width, ffirst, ssecond,
+                            moments):
+    """The argument checks of ``pairwise_velocity_pdf`` on the host, without a library call:
+    ``(n, dist_bin, vel_bin, ffirst, ssecond)`` as ints, or ValueError.  The bin numbers and the row range must be
+    integers (anything with ``__index__``); a fractional value is refused, not truncated."""
+    import operator
+    if kind not in _lib.PVPDF_KIND:
+        raise ValueError(f"kind must be one of {sorted(_lib.PVPDF_KIND)}, got {kind!r}")
+    pos_shape, vel_shape = tuple(pos_shape), tuple(vel_shape)
+    if len(pos_shape) != 2 or pos_shape[1] != 3 or vel_shape != pos_shape:
+        raise ValueError(f"pos and vel must both be (N, 3), got {pos_shape} and {vel_shape}")
+    n = pos_shape[0]
+    if n >= 1 << 31:
+        raise ValueError(f"N={n}: fewer than 2^31 objects")
+    for name, v in (("r", r), ("dist_width", dist_width), ("vel_width", vel_width)):
+        try:
+            v = float("nan") if isinstance(v, (str, bytes)) else float(v)
+        except (TypeError, ValueError):
+            v = float("nan")
+        if not (np.isfinite(v) and v > 0):
+            raise ValueError(f"{name} must be a positive, finite real number, got {v!r}")
+    if not np.float32(r) > 0:
+        raise ValueError(f"r={r} is not positive as a float32, the reference's type of r")
+    ints = dict(dist_bin=dist_bin, vel_bin=vel_bin, ffirst=ffirst, ssecond=n if ssecond is None else ssecond)
+    for name, v in ints.items():
+        try:
+            ints[name] = operator.index(v)
+        except TypeError:
+            raise ValueError(f"{name} must be an integer, got {v!r}") from None
+    dist_bin, vel_bin, ffirst, ssecond = ints.values()
+    if dist_bin < 1 or vel_bin < 1:
+        raise ValueError(f"dist_bin={dist_bin}, vel_bin={vel_bin}: at least one bin each")
+    if dist_bin * vel_bin > _lib.PVPDF_MAX_BINS:
+        raise ValueError(f"{dist_bin} x {vel_bin} bins: at most {_lib.PVPDF_MAX_BINS} counters")
+    if moments and dist_bin > _lib.PVPDF_MAX_MOMENT_ROWS:
+        raise ValueError(f"dist_bin={dist_bin}: the moments take at most {_lib.PVPDF_MAX_MOMENT_ROWS} distance bins")
+    if not 0 <= ffirst <= ssecond <= n:
+        raise ValueError(f"row range [{ffirst}, {ssecond}) must satisfy 0 <= ffirst <= ssecond <= N = {n}")
+    return n, dist_bin, vel_bin, ffirst, ssecond
+
+
+def pairwise_velocity_pdf(pos, vel, r, dist_bin, vel_bin, kind, dist_width=1.0, vel_width=1.0, ffirst=0, ssecond=None,
+                          moments=False):
+    """The (separation bin, velocity bin) pair counts of the reference's mean_pv_z_sign / mean_pv_radial
+    (particles/utils_cython/pairwise_velocity.pyx) on the GPU: ``(hist, outside)``, device tensors, int64 of
+    (dist_bin, vel_bin) and an int64 scalar; with ``moments`` also ``(count, s1, s2)``, (dist_bin,) int64 / float64 /
+    float64.  ``kind``: "z_sign" (v12 = (vz_j - vz_i) sign(z_j - z_i)) or "radial" (v12 = dv . dr / |dr|).  The
+    pair i < j is seen when |dr| <= float32(r) and ffirst <= i < ssecond; it counts in
+    ``hist[int(ds), int(vs)]``, ds = float32(|dr| / dist_width), vs = float32(v12 / vel_width + vel_bin // 2), when
+    int(ds) < dist_bin and 0 <= vs < vel_bin, else in ``outside``.  The moments are over the seen pairs of a row with
+    finite v12, whatever vs is.  ``pos`` / ``vel``: (N, 3), numpy arrays or device tensors, float32 or float64 (widened
+    to float64 on load).  ValueError, before any library call, for bad arguments.
+    ASTRILD_PVPDF_CELLS=0 forces one cell (all pairs) instead of the cell grid; ASTRILD_PVPDF_LDS=0 forces the
+    histogram into global memory, whatever its size."""
+    import os
+    n, dist_bin, vel_bin, ffirst, ssecond = check_pairwise_pdf_args(
+        np.shape(pos), np.shape(vel), r, dist_bin, vel_bin, kind, dist_width, vel_width, ffirst, ssecond, moments)
+    lib = _lib.lib()
+    p = as_device(pos)
+    v = as_device(vel)
+    p = p if p.dtype in _REAL else p.to(torch.float64)
+    v = v if v.dtype in _REAL else v.to(torch.float64)
+    single = os.environ.get("ASTRILD_PVPDF_CELLS", "1") == "0"
+    force_global = os.environ.get("ASTRILD_PVPDF_LDS", "1") == "0"
+    ws_bytes = lib.ast_pairwise_pdf_workspace_bytes(n, dist_bin, vel_bin, int(bool(moments)))
+    work = torch.empty(ws_bytes, dtype=torch.uint8, device=p.device)
+    hist = torch.empty((dist_bin, vel_bin), dtype=torch.int64, device=p.device)
+    outside = torch.empty((), dtype=torch.int64, device=p.device)
+    count = s1 = s2 = None
+    if moments:
+        count = torch.empty(dist_bin, dtype=torch.int64, device=p.device)
+        s1 = torch.empty(dist_bin, dtype=torch.float64, device=p.device)
+        s2 = torch.empty(dist_bin, dtype=torch.float64, device=p.device)
+    st = stream()
+    check(lib.ast_pairwise_pdf_prepare(ptr(p), real_code(p), ptr(v), real_code(v), n, ptr(work), ws_bytes, st),
+          "ast_pairwise_pdf_prepare")
+    check(lib.ast_pairwise_pdf(ptr(work), ws_bytes, n, _lib.PVPDF_KIND[kind], float(r), dist_bin, vel_bin,
+                               float(dist_width), float(vel_width), ffirst, ssecond, int(single), int(force_global),
+                               ptr(hist), ptr(outside), ptr(s1), ptr(s2), ptr(count), st), "ast_pairwise_pdf")
+    if moments:
+        return hist, outside, (count, s1, s2)
+    return hist, outside
+
+
 # ------------------------------------------------------------------ two-point correlation function
 def check_tpcf_edges(s_edges, mu_edges, boxsize):
     """halotools' argument checks of a periodic (s, mu) pair count, on the host: fp64 edges ``(s, mu)`` (``mu`` None

@@ -804,6 +804,54 @@ int ast_pairwise_tv_prepare(const void* pos_d, int pos_dtype, const void* vel_d,
 int ast_pairwise_tv(void* work_d, size_t work_bytes, size_t n, int binnr, double binwidth, int single_cell,
                     double* nom_d, double* denom_d, unsigned long long* counts_d, void* stream);
 
+/* ------------------------------------------------- pairwise-velocity histograms */
+
+/* The (separation bin, velocity bin) pair counts of particles/utils_cython/pairwise_velocity.pyx: mean_pv_z_sign
+ * (:194-253) and mean_pv_radial (:256-313).  For every unordered pair of original indices i < j, in fp64 and op by
+ * op, with the differences taken j - i:  d = sqrt((dx dx + dy dy) + dz dz); the pair is seen when d <= R,
+ * R = (double)(float)r (the reference declares `float r`), and first <= i < second (the reference's chunking of its
+ * i loop).  Its velocity is
+ *   AST_PVPDF_Z_SIGN:  v12 = (vz_j - vz_i) sign(z_j - z_i)           (sign = -1, 0, +1)
+ *   AST_PVPDF_RADIAL:  v12 = ((dvx dx + dvy dy) + dvz dz) / d         (mean_pv_radial does not run as shipped; this is
+ *                                                                     z_sign's rule with the radial velocity)
+ * and, rounded to float32 as the reference's `cdef float diff, dist`, ds = (float)(d / dist_width) and
+ * vs = (float)(v12 / vel_width + vel_bin / 2) (integer division).  The pair adds 1 to hist_d[a * vel_bin + b],
+ * a = (int)ds, b = (int)vs, when a < dist_bin and 0 <= vs < vel_bin; every other seen pair (NaN from coincident
+ * objects included) adds 1 to *outside_d, the reference's rubbish_counter - also where the reference raises
+ * IndexError (vs == vel_bin, a == dist_bin).  With the widths 1 this is the reference's own rule.
+ * Moments (s1_d, s2_d, mcount_d all given, dist_bin entries each; all NULL: none): over the seen pairs of row
+ * a < dist_bin with finite v12, whatever vs is, sum v12, sum v12^2 and their number.
+ * All outputs are written, not accumulated; all zero for n < 2 or first == second.  hist_d, *outside_d and mcount_d
+ * are exact and the same from call to call; s1_d / s2_d are fp64 sums in no fixed order (LDS atomics per wave, then
+ * fixed-order sums of the waves and workgroups - no global float atomics).
+ *
+ * Two calls on one workspace of ast_pairwise_pdf_workspace_bytes(n, dist_bin, vel_bin, moments) bytes (0: a bin count
+ * below 1, dist_bin * vel_bin > ast_pairwise_pdf_max_bins(), or moments with dist_bin > AST_PVPDF_MAX_MOMENT_ROWS):
+ * ast_pairwise_pdf_prepare (pairwise_velocity.pyx:194-313: the arrays ppos, vvel) widens pos_d, vel_d (n, 3) to fp64,
+ * keeps the original index and takes the bounding box; ast_pairwise_pdf (pairwise_velocity.pyx:194-313: the pair
+ * loops) sorts the objects into a cell grid of cells >= R over the bounding box (non-periodic; single_cell != 0: one
+ * cell, all pairs) and counts.  Histograms of up to ast_pairwise_pdf_lds_bins(dist_bin, moments) counters are
+ * counted in LDS (32-bit counters, flushed into hist_d with 64-bit integer atomics before they could overflow);
+ * larger ones, or any with force_global != 0, take one 64-bit integer atomic on hist_d per counted pair.  Both
+ * paths give the same counts.  n < 2^31. */
+#define AST_PVPDF_Z_SIGN 0
+#define AST_PVPDF_RADIAL 1
+#define AST_PVPDF_MAX_MOMENT_ROWS 480
+/* pairwise_velocity.pyx:194-313 */
+size_t ast_pairwise_pdf_workspace_bytes(size_t n, int dist_bin, int vel_bin, int moments);
+/* pairwise_velocity.pyx:194-313: the largest dist_bin * vel_bin (at least 2^22) */
+int ast_pairwise_pdf_max_bins(void);
+/* pairwise_velocity.pyx:194-313: the largest dist_bin * vel_bin that is counted in LDS */
+int ast_pairwise_pdf_lds_bins(int dist_bin, int moments);
+/* pairwise_velocity.pyx:194-313 */
+int ast_pairwise_pdf_prepare(const void* pos_d, int pos_dtype, const void* vel_d, int vel_dtype, size_t n, void* work_d,
+                             size_t work_bytes, void* stream);
+/* pairwise_velocity.pyx:194-313 */
+int ast_pairwise_pdf(void* work_d, size_t work_bytes, size_t n, int kind, double r, int dist_bin, int vel_bin,
+                     double dist_width, double vel_width, size_t first, size_t second, int single_cell,
+                     int force_global, unsigned long long* hist_d, unsigned long long* outside_d, double* s1_d,
+                     double* s2_d, unsigned long long* mcount_d, void* stream);
+
 /* ------------------------------------------------- two-point correlation function */
 
 /* Pair counts of the two-point correlation function of a periodic box: particles/hutils/tpcf.py (TPCF.compute /
