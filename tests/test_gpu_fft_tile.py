@@ -291,6 +291,57 @@ def test_batched_inverse_passes_equal_the_single_shell_calls(hip, n):
     assert hip.ast_fft_tile_c2r_3d_batch(dev.ptr(spec), wp, op, 0, n, lo, hi, 1, 1.0, 3, n // 2, dev.stream()) < 0      # pitch < n/2+1
 
 
+def test_inverse_tile_passes_at_side_1024(hip):
+    """The 1024 instantiations of the inverse passes (launch_c2r<16, 32, 16>, the masked x / y passes with 32 x 32 radices) -
+    what device.bispectrum sends a 1024^3 fp32 grid through: the whole inverse and three masked ones (the zero mode alone, a
+    small shell, one that reaches past the Nyquist disc and clamps kmax) against float64 irfftn of the same spectrum, work
+    arrays poisoned with NaN; the batched call bit-identical to the single-shell calls, x / y passes shell by shell and
+    three at a time, natural and line-aligned pitch.  (Not a parameter of the 8-shell batch test above: > 100 GB.)"""
+    from astrild_amd import device as dev
+    from tests import bispectrum_reference as br
+    torch.cuda.set_device(0)
+    n = 1024
+
+    def poisoned(pitch):
+        w = torch.empty((n, n, pitch), dtype=torch.complex64, device="cuda")
+        torch.view_as_real(w).fill_(float("nan"))
+        return w
+
+    g = torch.Generator(device="cuda").manual_seed(n)
+    t = torch.randn((n, n, n), generator=g, device="cuda", dtype=torch.float32)
+    fmax = t.abs().max().item()
+    spec = dev.r2c(t)
+    del t
+    keep = spec.clone()
+    back = dev.c2r_tile(spec)
+    assert torch.equal(spec, keep)
+    ref = br.shell_field(spec, 0, 0)                               # float64 irfftn of the whole spectrum, slab by slab
+    err = ref.sub_(back).abs_().max().item()
+    del back, ref
+    assert err < 5e-6 * fmax, err
+    shells = [(0, 1), (1, 9), (n // 2 - 8, n // 2 + 40)]
+    m2 = br.m2_half(n, "cuda")
+    singles = []
+    for lo, hi in shells:
+        got = dev.c2r_tile(spec, work=poisoned(n // 2 + 1), m_lo=lo, m_hi=hi)
+        assert torch.isfinite(got).all(), (lo, hi)
+        ref = br.shell_field(spec, lo, hi, m2)
+        scale = ref.abs().max().item()
+        err = ref.sub_(got).abs_().max().item()
+        del ref
+        assert err < 5e-6 * scale, (lo, hi, err / scale)
+        singles.append(got)
+    del m2
+    outs = [torch.empty_like(s) for s in singles]
+    for pitch in (n // 2 + 1, dev.tile_work_pitch(n)):
+        for xy in (1, 3):
+            for o in outs:
+                o.fill_(float("nan"))
+            got = dev.c2r_tile_batch(spec, shells, [poisoned(pitch) for _ in shells], outs=outs, xy_batch=xy)
+            assert all(torch.equal(a, b) for a, b in zip(got, singles)), (pitch, xy)
+    assert torch.equal(spec, keep)
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
 def test_triple_product_sums_one_pass(hip, dtype):
     """All triangle sums in one pass over the fields (ast_triple_product_sums) against float64 numpy; ragged cell
