@@ -494,12 +494,75 @@ __device__ constexpr double kS16f[16] = {0.0, -0.38268343236508977, -0.707106781
                                          0.38268343236508977, 0.70710678118654752, 0.92387953251128674, 1.0,
                                          0.92387953251128674, 0.70710678118654752, 0.38268343236508977};
 
+// Outputs 0 .. 4 of the 8-point transform of real samples, E[k] = sum_j e[j] e^{-2 pi i j k / 8}, in double.
+__device__ inline void real_dft8_low5(const double (&e)[8], double (&er)[5], double (&ei)[5]) {
+    const double a0 = e[0] + e[4], a1 = e[1] + e[5], a2 = e[2] + e[6], a3 = e[3] + e[7];
+    const double b0 = e[0] - e[4], b1 = e[1] - e[5], b2 = e[2] - e[6], b3 = e[3] - e[7];
+    const double s02 = a0 + a2, s13 = a1 + a3;
+    er[0] = s02 + s13;
+    ei[0] = 0.0;
+    er[4] = s02 - s13;
+    ei[4] = 0.0;
+    er[2] = a0 - a2;
+    ei[2] = a3 - a1;
+    const double pc = kC16f[2] * (b1 - b3), qc = kC16f[2] * (b1 + b3);
+    er[1] = b0 + pc;
+    ei[1] = -b2 - qc;
+    er[3] = b0 - pc;
+    ei[3] = b2 - qc;
+}
+// Outputs 0 .. 6 of the R1-point transform of real samples, T[k] = sum_j f[j] e^{-2 pi i j k / R1}, R1 = 16 or 8, in
+// double with constant twiddles, handed to emit(k, re, im) in the order 1, 3, 5, 0, 2, 4, 6 (each output is used up
+// before the next group is formed: the z pass has no registers to hold all seven).  R1 = 16: stage one is
+// f[j] +- f[j + 8]; the even outputs are the 8-point transform of the sums, the odd ones come from the differences d,
+// whose terms j and 8 - j share a cosine (opposite sign) and a sine.  R1 = 8: outputs 5 and 6 are the conjugates of 3
+// and 2.  (The direct sums this replaces were 7 x R1 terms per parity: about 330 double operations a thread against 125.)
+template <int R1, typename Emit>
+__device__ inline void real_dft_low7(const double (&f)[R1], Emit&& emit) {
+    static_assert(R1 == 16 || R1 == 8, "16- or 8-point transform");
+    double er[5], ei[5];
+    if constexpr (R1 == 8) {
+        real_dft8_low5(f, er, ei);
+        emit(1, er[1], ei[1]);
+        emit(3, er[3], ei[3]);
+        emit(5, er[3], -ei[3]);
+        emit(0, er[0], ei[0]);
+        emit(2, er[2], ei[2]);
+        emit(4, er[4], ei[4]);
+        emit(6, er[2], -ei[2]);
+    } else {
+        double d[8], e[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            d[j] = f[j] - f[j + 8];
+            e[j] = f[j] + f[j + 8];
+        }
+        double g[4], s[4];                                       // cosine and sine partners, j = 1 .. 3
+#pragma unroll
+        for (int j = 1; j < 4; ++j) { g[j] = d[j] - d[8 - j]; s[j] = d[j] + d[8 - j]; }
+#pragma unroll
+        for (int k = 1; k < 6; k += 2) {
+            double xr = d[0], xi = (k & 2) ? d[4] : -d[4];       // e^{-2 pi i 4 k / 16} = -i, +i, -i
+#pragma unroll
+            for (int j = 1; j < 4; ++j) {
+                xr = fma(g[j], kC16f[(j * k) % 16], xr);
+                xi = fma(s[j], kS16f[(j * k) % 16], xi);
+            }
+            emit(k, xr, xi);
+        }
+        real_dft8_low5(e, er, ei);
+#pragma unroll
+        for (int m = 0; m < 4; ++m) emit(2 * m, er[m], ei[m]);
+    }
+}
+
 // LOWK: the thread's 2 R1 samples x[2 R2 n1 + 2 n2 + p] are in registers right after the load, so the low-k channel's
 // z sums S_kz = sum_z x[z] e^{-2 pi i kz z / N}, kz <= 6, are formed here in double instead of by a second pass over
-// the grid (lowk_z_kernel: 4.3 GB, 1.2 ms at 1024^3): per p the R1-term sum over n1 with the R1-th roots of unity as
-// constants (e^{-2 pi i 2 R2 / N} = e^{-2 pi i / R1}), then T_0 A + T_1 B with the lane's factors A = w^{2 kz n2},
-// B = w^{kz (2 n2 + 1)} (table lowk_lane, double), then a transposed reduction over the row's R2 lanes.  Output as
-// lowk_z_kernel's.
+// the grid (lowk_z_kernel: 4.3 GB, 1.2 ms at 1024^3): per p the R1-point real-input transform over n1 of which only
+// the outputs 0 .. 6 are formed (real_dft_low7; e^{-2 pi i 2 R2 / N} = e^{-2 pi i / R1}), then T_0 A^kz + T_1 B^kz with
+// the lane's factors A = w^{2 n2}, B = w^{2 n2 + 1} (two entries of the table lowk_lane, double, fetched before the
+// row; their powers by repeated multiplication - a few ulp), then a transposed reduction over the row's R2 lanes.
+// Output as lowk_z_kernel's.
 // M = R1*R2.  One workgroup transforms C rows.
 // FOLDW = 2 / 3 (CIC / TSC): `in` is the grid a deferred-fold paint left (AST_PAINT_DEFER_FOLD) and `rec`
 // its halo records; the up to three record lines that end in a border row are added as the row is
@@ -533,14 +596,12 @@ rows_r2c_kernel(const float* __restrict__ in, float2* __restrict__ out, const fl
         // z[j] = x[2j] + i x[2j+1]; rows past the end re-read the last one (unconditional loads)
         const float2* zin = reinterpret_cast<const float2*>(in + min(row0 + r, nrows - 1) * in_pitch);
         float2 v[R1];
-#pragma unroll
-        for (int n1 = 0; n1 < R1; ++n1) v[n1] = ld_stream<(N >= 1024)>(zin + n1 * R2 + n2);
-        if (FOLDW != 0) {
+        const float* src[3];
+        int ns = 0;
+        if (FOLDW != 0) {                    // the record lines of this row, found before any load is issued
             constexpr int W = FOLDW != 0 ? FOLDW : 2;
             const int ng = (int)(2 * M);
             const size_t row = min(row0 + r, nrows - 1);
-            const float* src[3];
-            int ns;
             if (sf.ntx == 0) {
                 const int xb = sf.xb0 + (int)(row / ng), trow = xb / ast::TX;
                 ns = !sf.ranges || (trow >= sf.row_lo && trow < sf.row_hi)
@@ -550,22 +611,32 @@ rows_r2c_kernel(const float* __restrict__ in, float2* __restrict__ out, const fl
                 ns = trow >= sf.row_lo && trow < sf.row_hi
                          ? ast::halo_sources<float, W>(rec, xb, (int)(row % ng), ng, sf.ntx, ng / ast::TY, src, false) : 0;
             }
-            if (ns > 0) {                    // 15 of 64 rows (CIC); the loads and adds stay inside the branch
+        }
+#pragma unroll
+        for (int n1 = 0; n1 < R1; ++n1) v[n1] = ld_stream<(N >= 1024)>(zin + n1 * R2 + n2);
+        if (FOLDW != 0 && ns > 0) {          // 15 of 64 rows (CIC); the record loads follow the row's at once, inside the branch
+            auto rec_ld = [&](int s, int n1) { return ld_stream<(N >= 1024)>(reinterpret_cast<const float2*>(src[s]) + n1 * R2 + n2); };
+            if (ns == 1) {                   // one record: straight onto the row (the bits of h = rec; v += h)
+#pragma unroll
+                for (int n1 = 0; n1 < R1; ++n1) {
+                    const float2 t = rec_ld(0, n1);
+                    v[n1].x += t.x;
+                    v[n1].y += t.y;
+                }
+            } else {                         // sum of the records first, then onto the row: the order of column_fold_kernel
                 float2 h[R1];
 #pragma unroll
-                for (int n1 = 0; n1 < R1; ++n1) h[n1] = reinterpret_cast<const float2*>(src[0])[n1 * R2 + n2];
-                if (ns > 1) {
+                for (int n1 = 0; n1 < R1; ++n1) h[n1] = rec_ld(0, n1);
 #pragma unroll
-                    for (int n1 = 0; n1 < R1; ++n1) {
-                        const float2 t = reinterpret_cast<const float2*>(src[1])[n1 * R2 + n2];
-                        h[n1].x += t.x;
-                        h[n1].y += t.y;
-                    }
+                for (int n1 = 0; n1 < R1; ++n1) {
+                    const float2 t = rec_ld(1, n1);
+                    h[n1].x += t.x;
+                    h[n1].y += t.y;
                 }
                 if (ns > 2) {
 #pragma unroll
                     for (int n1 = 0; n1 < R1; ++n1) {
-                        const float2 t = reinterpret_cast<const float2*>(src[2])[n1 * R2 + n2];
+                        const float2 t = rec_ld(2, n1);
                         h[n1].x += t.x;
                         h[n1].y += t.y;
                     }
@@ -579,6 +650,9 @@ rows_r2c_kernel(const float* __restrict__ in, float2* __restrict__ out, const fl
         }
         if (LOWK) {
             static_assert(!LOWK || ((R1 == 16 || R1 == 8) && (R2 == 32 || R2 == 16) && MBOX_FWD == 6), "R1-th roots from the 16th-root table; 32 or 16 lanes per row");
+            // lane factors w^{2 n2} and w^{2 n2 + 1}, w = e^{-2 pi i / N}, fetched behind the row (and its records): the
+            // first transform below covers their latency, and they do not sit in registers while the fold holds h[]
+            const double2 la = lowk_lane[(n2 * (MBOX_FWD + 1) + 1) * 2], lb = lowk_lane[(n2 * (MBOX_FWD + 1) + 1) * 2 + 1];
             double acc[14];
 #pragma unroll
             for (int e = 0; e < 14; ++e) acc[e] = 0.0;
@@ -587,22 +661,17 @@ rows_r2c_kernel(const float* __restrict__ in, float2* __restrict__ out, const fl
                 double f[R1];
 #pragma unroll
                 for (int n1 = 0; n1 < R1; ++n1) f[n1] = (double)(p ? v[n1].y : v[n1].x);
-#pragma unroll
-                for (int kz = 0; kz <= MBOX_FWD; ++kz) {
-                    double tr = 0.0, ti = 0.0;
-#pragma unroll
-                    for (int n1 = 0; n1 < R1; ++n1) {
-                        const int rr = ((kz * n1) % R1) * (16 / R1);     // e^{-2 pi i kz n1 / R1}: a compile-time constant
-                        if (rr == 0) tr += f[n1];
-                        else if (rr == 4) ti -= f[n1];
-                        else if (rr == 8) tr -= f[n1];
-                        else if (rr == 12) ti += f[n1];
-                        else { tr = fma(f[n1], kC16f[rr], tr); ti = fma(f[n1], kS16f[rr], ti); }
-                    }
-                    const double2 a = lowk_lane[(n2 * (MBOX_FWD + 1) + kz) * 2 + p];
+                // lane factor^kz in the order the outputs come: base, ^3, ^5, then base^2, ^4, ^6 (steps of base^2)
+                const double2 base = p ? lb : la;
+                const double2 sq = make_double2(fma(base.x, base.x, -(base.y * base.y)), 2.0 * (base.x * base.y));
+                double2 a = base;
+                real_dft_low7<R1>(f, [&](int kz, double tr, double ti) __attribute__((always_inline)) {
+                    if (kz == 0) { acc[0] += tr; return; }       // (T_0 is real)
+                    if (kz == 2) a = sq;
+                    else if (kz != 1) a = make_double2(fma(a.x, sq.x, -(a.y * sq.y)), fma(a.x, sq.y, a.y * sq.x));
                     acc[2 * kz] = fma(a.x, tr, fma(-a.y, ti, acc[2 * kz]));
                     acc[2 * kz + 1] = fma(a.x, ti, fma(a.y, tr, acc[2 * kz + 1]));
-                }
+                });
             }
             // 14 sums over the row's R2 lanes (a wave holds 64 / R2 rows): 14 -> 7 (+1 zero) -> 4 -> 2 -> 1, with 32 lanes
             // then the last pair
