@@ -101,6 +101,9 @@ SIGNATURES = {
     "ast_lowk_shell_sums": (_i, [_vp, _sz, _d, _i, _vp, _vp]),
     "ast_paint_tiled_halo": (_i, [_vp, _i, _i, _sz, _i, _i, _i, ct.POINTER(ct.c_void_p)]),
     "ast_power_bin_1d": (_i, [_vp, _vp, _i, _i, _d, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
+    "ast_power_bin_2d_lds_fits": (_i, [_i, _i, _i]),
+    "ast_power_bin_2d": (_i, [_vp, _vp, _i, _i, _d, _i, _i, _i, _i, _i, _i, ct.POINTER(_i), _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "ast_rsd_shift": (_i, [_vp, _vp, _i, _sz, _i, _d, _d, _vp, _vp]),
     "ast_interlace_compensate": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "ast_shell_filter": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "ast_shell_mask_real": (_i, [_vp, _i, _i, _i, _vp]),

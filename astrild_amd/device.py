@@ -724,6 +724,163 @@ def finish_power(ksum, psum, nmodes):
         return {"k": ks / nm, "power": ps / nm, "modes": nm, "shotnoise": 0.0}
 
 
+POLES_ALLOWED = (0, 2, 4, 6, 8)
+MAX_NMU = 1024
+
+
+def check_fftpower_2d_args(Nmu, los, poles):
+    """Host-only argument check of the (k, mu) / multipole binning: ``(Nmu, los, poles)`` as ints and a tuple, or
+    ValueError.  ``Nmu`` in 1 .. 1024; ``los`` a box axis 0, 1 or 2; ``poles`` distinct even orders from
+    {0, 2, 4, 6, 8} (may be empty) - the spectrum is folded onto mu in [0, 1] and cannot represent an odd multipole."""
+    if isinstance(Nmu, bool) or not isinstance(Nmu, (int, np.integer)) or not 1 <= Nmu <= MAX_NMU:
+        raise ValueError(f"Nmu must be an integer in 1 .. {MAX_NMU}, got {Nmu!r}")
+    if isinstance(los, bool) or not isinstance(los, (int, np.integer)) or los not in (0, 1, 2):
+        raise ValueError(f"los must be a box axis 0, 1 or 2, got {los!r}")
+    poles = tuple(() if poles is None else poles)
+    for l in poles:
+        if isinstance(l, bool) or not isinstance(l, (int, np.integer)) or l not in POLES_ALLOWED:
+            raise ValueError(f"poles must be even orders from {POLES_ALLOWED} (odd multipoles vanish on the folded "
+                             f"spectrum), got {l!r}")
+    if len(set(poles)) != len(poles):
+        raise ValueError(f"poles repeat an order: {poles}")
+    return int(Nmu), int(los), tuple(int(l) for l in poles)
+
+
+def _poles_arg(poles):
+    return (ct.c_int * max(len(poles), 1))(*poles)
+
+
+def shell_geometry_2d(nmesh, boxsize, Nmu, los, i0=None, i1=None, binning=None):
+    """(sum w|k|, sum w mu, sum w) per (shell, mu bin) of a spectrum block, (nmesh/2-1, Nmu) each - data independent,
+    cached."""
+    Nmu, los, _ = check_fftpower_2d_args(Nmu, los, ())
+    n = int(nmesh)
+    i0 = (0, n) if i0 is None else tuple(i0)
+    i1 = (0, n) if i1 is None else tuple(i1)
+    key = (torch.cuda.current_device(), n, float(boxsize), i0, i1, _bin_code(binning), Nmu, los)
+    hit = _geom_cache.get(key)
+    if hit is None:
+        nb = n // 2 - 1
+        ksum = torch.zeros((nb, Nmu), dtype=torch.float64, device=device())
+        musum = torch.zeros((nb, Nmu), dtype=torch.float64, device=device())
+        nmodes = torch.zeros((nb, Nmu), dtype=torch.int64, device=device())
+        check(_lib.lib().ast_power_bin_2d(None, None, F64, n, float(boxsize), int(i0[0]), int(i0[1]), int(i1[0]), int(i1[1]),
+                                          los, Nmu, None, 0, ptr(ksum), ptr(musum), ptr(nmodes), None, None,
+                                          _bin_code(binning), stream()), "ast_power_bin_2d[geometry]")
+        hit = _geom_cache[key] = (ksum, musum, nmodes)
+    return hit
+
+
+def power_bin_2d(spec1, spec2, nmesh, boxsize, Nmu=5, los=2, poles=(0, 2, 4), i0=None, i1=None, psum=None, polesum=None,
+                 binning=None):
+    """Wedge and multipole sums (ksum, musum, psum, nmodes, polesum) of a block of the half spectrum (device tensors):
+    the first four (nmesh/2-1, Nmu), polesum (len(poles), nmesh/2-1) without the factor 2l + 1 - see ast_power_bin_2d.
+    ``psum`` / ``polesum`` given: accumulated into (blocks and ranks add)."""
+    Nmu, los, poles = check_fftpower_2d_args(Nmu, los, poles)
+    n = int(nmesh)
+    nb = n // 2 - 1
+    i0 = (0, n) if i0 is None else tuple(i0)
+    i1 = (0, n) if i1 is None else tuple(i1)
+    assert spec1.is_cuda and spec1.is_contiguous() and spec1.numel() == i0[1] * i1[1] * (n // 2 + 1)
+    code = _CPLX[spec1.dtype]
+    if spec2 is not None:
+        assert spec2.dtype == spec1.dtype and spec2.numel() == spec1.numel() and spec2.is_contiguous()
+    if psum is None:
+        psum = torch.zeros((nb, Nmu), dtype=torch.float64, device=spec1.device)
+    if polesum is None:
+        polesum = torch.zeros((len(poles), nb), dtype=torch.float64, device=spec1.device)
+    assert psum.dtype == torch.float64 and tuple(psum.shape) == (nb, Nmu) and psum.is_contiguous()
+    assert polesum.dtype == torch.float64 and tuple(polesum.shape) == (len(poles), nb) and polesum.is_contiguous()
+    ksum, musum, nmodes = shell_geometry_2d(n, boxsize, Nmu, los, i0, i1, binning)
+    check(_lib.lib().ast_power_bin_2d(ptr(spec1), ptr(spec2), code, n, float(boxsize), int(i0[0]), int(i0[1]),
+                                      int(i1[0]), int(i1[1]), los, Nmu, _poles_arg(poles), len(poles), None, None, None,
+                                      ptr(psum), ptr(polesum) if len(poles) else None, _bin_code(binning), stream()),
+          "ast_power_bin_2d")
+    return ksum, musum, psum, nmodes, polesum
+
+
+def finish_power_2d(ksum, musum, psum, nmodes, polesum, poles=(0, 2, 4), shotnoise=0.0):
+    """Wedges k, mu, power = sums / modes on the host (empty bins NaN like finish_power) and the multipoles
+    ``power_l = (2l + 1) polesum_l / modes`` of the 1-D shells, whose k and modes are the wedge sums added over mu."""
+    ks, mus, ps, nm, pol = (t.cpu().numpy() for t in (ksum, musum, psum, nmodes, polesum))
+    nm1 = nm.sum(axis=1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        res = {"k": ks / nm, "mu": mus / nm, "power": ps / nm, "modes": nm, "shotnoise": float(shotnoise),
+               "poles": {"k": ks.sum(axis=1) / nm1, "modes": nm1}}
+        for q, l in enumerate(poles):
+            res["poles"]["power_%d" % l] = (2 * l + 1) * pol[q] / nm1
+    return res
+
+
+def fftpower_2d(field1, boxsize, field2=None, Nmu=5, los=2, poles=(0, 2, 4), binning=None):
+    """``FFTPower(first, mode="2d", Nmu=, los=, poles=, kmin=2*pi/L[, second])`` for in-memory grids, the line of sight
+    along box axis ``los``: r2c, then the (k, mu) / Legendre binning of the half spectrum (ast_power_bin_2d).  fp32
+    grids are transformed in double, as in the non-fused branch of :func:`fftpower_1d` and for its reason."""
+    Nmu, los, poles = check_fftpower_2d_args(Nmu, los, poles)
+    n = field1.shape[0]
+    assert tuple(field1.shape) == (n, n, n) and n % 2 == 0
+    if field1.dtype == torch.float32:
+        field1 = field1.double()
+        field2 = None if field2 is None else field2.double()
+    s1 = r2c(field1)
+    s2 = None if field2 is None else r2c(field2)
+    return finish_power_2d(*power_bin_2d(s1, s2, n, boxsize, Nmu, los, poles, binning=binning), poles=poles)
+
+
+def rsd_shift(pos, vel, boxsize, los=2, factor=0.01, out=None):
+    """Redshift-space positions ``s = pos; s[:, los] += factor * vel[:, los]`` with one periodic wrap into [0, boxsize)
+    (ast_rsd_shift); ``factor`` 0.01 is TPCF's ``vel / 100``.  (N, 3) device tensors of one dtype, float32 or float64,
+    arithmetic in that dtype.  Like TPCF, a shift that one wrap does not bring back into the box (more than a box
+    length, or a position outside it) is a ValueError; the test reads the extremes of the shifted column back (one host
+    sync per call, like tpcf_pair_counts' bounds).  ``out`` may be ``pos``: the shift then runs into a scratch tensor
+    that is copied over ``pos`` only once it has passed, so a rejected call leaves the caller's positions as they
+    were; a separate ``out`` holds the unwrapped result when the call raises."""
+    if los not in (0, 1, 2):
+        raise ValueError(f"los must be 0, 1 or 2, got {los}")
+    boxsize = float(boxsize)
+    if not (np.isfinite(boxsize) and boxsize > 0):
+        raise ValueError(f"boxsize must be positive and finite, got {boxsize}")
+    n = pos.shape[0] if pos.dim() == 2 else -1
+    if tuple(pos.shape) != (n, 3) or tuple(vel.shape) != (n, 3) or pos.dtype not in _REAL or vel.dtype != pos.dtype:
+        raise ValueError(f"pos and vel must be (N, 3) of one dtype, float32 or float64: got {tuple(pos.shape)} "
+                         f"{pos.dtype} and {tuple(vel.shape)} {vel.dtype}")
+    assert pos.is_cuda and vel.is_cuda and pos.is_contiguous() and vel.is_contiguous()
+    if out is not None:
+        assert out.is_cuda and out.is_contiguous() and out.dtype == pos.dtype and out.shape == pos.shape
+    in_place = out is not None and out.data_ptr() == pos.data_ptr()
+    res = torch.empty_like(pos) if out is None or in_place else out
+    check(_lib.lib().ast_rsd_shift(ptr(pos), ptr(vel), real_code(pos), n, int(los), float(factor), boxsize, ptr(res),
+                                   stream()), "ast_rsd_shift")
+    if n:
+        lo, hi = (float(v) for v in torch.aminmax(res[:, los]))
+        if not (lo >= 0.0 and hi < boxsize):
+            raise ValueError(f"positions after the redshift-space shift and one wrap must lie in [0, {boxsize}): "
+                             f"min {lo}, max {hi}")
+    if in_place:
+        out.copy_(res)
+        return out
+    return res
+
+
+def catalog_power_2d(pos1, mass1, nmesh, boxsize, window="tsc", interlaced=True, compensated=True, pos2=None, mass2=None,
+                     vel1=None, vel2=None, rsd_factor=0.01, Nmu=5, los=2, poles=(0, 2, 4)):
+    """``FFTPower(CatalogMesh(cat1, ...), mode="2d", Nmu=, los=, poles=[, second=CatalogMesh(cat2, ...)])`` with the
+    catalogues moved to redshift space first where velocities are given (:func:`rsd_shift`): the dict of
+    :func:`finish_power_2d`; the shot noise is reported, not subtracted (auto: L^3 sum w^2 / (sum w)^2; cross: 0)."""
+    Nmu, los, poles = check_fftpower_2d_args(Nmu, los, poles)
+    n = int(nmesh)
+    if vel1 is not None:
+        pos1 = rsd_shift(pos1, vel1, boxsize, los, rsd_factor)
+    c1, sn = catalog_mesh_complex(pos1, mass1, n, boxsize, window, interlaced, compensated)
+    c2 = None
+    if pos2 is not None:
+        if vel2 is not None:
+            pos2 = rsd_shift(pos2, vel2, boxsize, los, rsd_factor)
+        c2, _ = catalog_mesh_complex(pos2, mass2, n, boxsize, window, interlaced, compensated)
+        sn = 0.0
+    return finish_power_2d(*power_bin_2d(c1, c2, n, boxsize, Nmu, los, poles), poles=poles, shotnoise=sn)
+
+
 _power_scratch = {}
 
 

@@ -49,11 +49,30 @@ class PowerSpectrum3D:
         snap_nrs: Optional[List[int]] = None,
         dir_out: Optional[str] = None,
         save: bool = True,
+        mode: str = "1d",
+        Nmu: int = 5,
+        los: int = 2,
+        poles: Tuple[int, ...] = (0, 2, 4),
     ) -> Union[None, dict]:
         """Power spectrum of particle quantities, same call as power_spectrum_3d.py:33-81: one file
         description -> auto spectra, two -> cross spectra of the paired files; one spectrum per snapshot.
-        Returns {"k": {snap_%d: k}, "P": {snap_%d: P}} when ``save`` is False, else writes pk_<quantities>.h5."""
+        Returns {"k": {snap_%d: k}, "P": {snap_%d: P}} when ``save`` is False, else writes pk_<quantities>.h5.
+
+        ``mode="2d"`` (no reference counterpart; nbodykit's ``FFTPower(mode="2d", Nmu=, los=, poles=)``): P(k, mu) in
+        ``Nmu`` bins of mu about the box axis ``los`` and the multipoles ``poles``.  Returns {snap_%d: the dict of
+        :meth:`_power_spectrum_2d`} when ``save`` is False, else writes pkmu_<quantities>.h5."""
+        if mode not in ("1d", "2d"):
+            raise ValueError(f"mode must be '1d' or '2d', got {mode!r}")
+        if mode == "2d":
+            Nmu, los, poles = dev.check_fftpower_2d_args(Nmu, los, poles)
         jobs = self._jobs(file_dsc, snap_nrs)
+        if mode == "2d":
+            pkmu = self._spectra(quantities, jobs, cross=len(file_dsc) > 1,
+                                 spectrum=lambda *maps: self._power_spectrum_2d(*maps, Nmu=Nmu, los=los, poles=poles))
+            if save:
+                self._save_results_2d(quantities, pkmu)
+                return None
+            return pkmu
         pk = self._spectra(quantities, jobs, cross=len(file_dsc) > 1)
         if save:
             self._save_results(quantities, pk)
@@ -76,10 +95,11 @@ class PowerSpectrum3D:
             columns.append(self.sim.get_file_paths(dsc, path, "max"))
         return list(zip(np.sort(snap_nrs), zip(*columns)))
 
-    def _spectra(self, quantity, jobs, cross) -> dict:
+    def _spectra(self, quantity, jobs, cross, spectrum=None) -> dict:
         """One spectrum per job.  Auto: the ``quantity`` column of the file; cross: both files as they are
-        (the reference passes quantity=None there, :120-121)."""
-        pk = {"k": {}, "P": {}}
+        (the reference passes quantity=None there, :120-121).  ``spectrum`` (maps -> result): what is computed of a
+        snapshot's grids instead of (k, P); the results come back as {snap_%d: result}."""
+        pk = {"k": {}, "P": {}} if spectrum is None else {}
         # The reference reads, grids and transforms snapshot after snapshot (power_spectrum_3d.py:83-110).  Here the NEXT
         # snapshot's files are read (and .npy grids staged in page-locked memory) by a loader thread while the current one
         # is uploaded and transformed: a 512^3 float64 grid is 19 ms of PCIe next to ~6 ms of GPU work, and the disk read
@@ -104,7 +124,12 @@ class PowerSpectrum3D:
                 maps = [self._to_device(item) for item in loaded]
                 if maps[0].dim() != 3:
                     raise PowerSpectrum3DWarning(f"{maps[0].dim()}D is not supported :-(")
+                if spectrum is not None:
+                    pk["snap_%d" % snap_nr] = spectrum(*maps)
+                    continue
                 pk["k"]["snap_%d" % snap_nr], pk["P"]["snap_%d" % snap_nr] = self._power_spectrum_3d(*maps)
+        if spectrum is not None:
+            return pk
         ks = list(pk["k"].values())
         if len(ks) > 1:                     # the reference's check that snapshots share their wavenumbers
             assert np.sum(ks[0]) == np.sum(ks[1])
@@ -228,6 +253,52 @@ class PowerSpectrum3D:
         r = dev.catalog_power_1d(as_dev(pos1), as_dev(mass1), int(self.sim.domain_level), self.sim.boxsize, window,
                                  interlaced, compensated, pos2=as_dev(pos2), mass2=as_dev(mass2))
         return np.array(r["k"]), np.array(r["power"] - r["shotnoise"])
+
+    def _power_spectrum_2d(self, value_map1, value_map2=None, Nmu: int = 5, los: int = 2, poles=(0, 2, 4)) -> dict:
+        """P(k, mu) and multipoles of one grid (or the cross spectrum of two), ``FFTPower(mode="2d", Nmu=, los=, poles=,
+        kmin=2*pi/L)`` semantics with the line of sight along box axis ``los``: {"k", "mu", "power", "modes":
+        (Nmesh/2-1, Nmu); "shotnoise"; "poles": {"k", "modes", "power_<l>"}} (device.fftpower_2d; DESIGN.md).  Accepts
+        numpy arrays or CUDA tensors."""
+        f1 = dev.as_device(value_map1, self.dtype)
+        f2 = None if value_map2 is None else dev.as_device(value_map2, self.dtype)
+        n = int(self.sim.domain_level)
+        if tuple(f1.shape) != (n, n, n):
+            raise PowerSpectrum3DWarning(f"value_map shape {tuple(f1.shape)} does not match Nmesh={n}")
+        return dev.fftpower_2d(f1, self.sim.boxsize, f2, Nmu=Nmu, los=los, poles=poles)
+
+    def _power_spectrum_2d_catalog(self, pos1, mass1=None, pos2=None, mass2=None, vel1=None, vel2=None,
+                                   rsd_factor: float = 0.01, window: str = "tsc", interlaced: bool = True,
+                                   compensated: bool = True, Nmu: int = 5, los: int = 2, poles=(0, 2, 4)) -> dict:
+        """The same for PARTICLE catalogues with the mesh parameters of :meth:`_power_spectrum_3d_catalog`; with
+        velocities the catalogue is moved to redshift space first, ``pos[:, los] += rsd_factor * vel[:, los]`` and one
+        periodic wrap (TPCF's shift).  The shot noise is reported in the dict, not subtracted."""
+        as_dev = lambda a: None if a is None else dev.as_device(np.ascontiguousarray(a), self.dtype)
+        return dev.catalog_power_2d(as_dev(pos1), as_dev(mass1), int(self.sim.domain_level), self.sim.boxsize, window,
+                                    interlaced, compensated, pos2=as_dev(pos2), mass2=as_dev(mass2), vel1=as_dev(vel1),
+                                    vel2=as_dev(vel2), rsd_factor=rsd_factor, Nmu=Nmu, los=los, poles=poles)
+
+    @staticmethod
+    def _frames_2d(res: dict):
+        """(wedge frame: index k of the shell, one column per mu-bin centre; poles frame: index k, columns P<l>, modes)
+        of one snapshot's mode-2d result."""
+        nmu = res["power"].shape[1]
+        k1 = res["poles"]["k"]
+        wedges = pd.DataFrame(res["power"], index=pd.Index(k1, name="k"), columns=(np.arange(nmu) + 0.5) / nmu)
+        cols = {"P%s" % key[len("power_"):]: val for key, val in res["poles"].items() if key.startswith("power_")}
+        cols["modes"] = res["poles"]["modes"]
+        return wedges, pd.DataFrame(cols, index=pd.Index(k1, name="k"))
+
+    def _save_results_2d(self, quantity: List[str], pkmu: dict) -> None:
+        """Per snapshot the frames of :meth:`_frames_2d` under the keys snap_%d_pkmu and snap_%d_poles ->
+        pkmu_<quantity>.h5."""
+        filename = self.sim.dirs["out"] + "pkmu_%s.h5" % (("_").join(quantity))
+        IO._remove_existing_file(filename)
+        print(f"Saving results to -> {filename}")
+        first = True
+        for snap, res in pkmu.items():
+            for frame, name in zip(self._frames_2d(res), ("pkmu", "poles")):
+                frame.to_hdf(filename, key="%s_%s" % (snap, name), mode="w" if first else "a")
+                first = False
 
     def _save_results(self, quantity: List[str], pk: dict) -> None:
         """DataFrame(index=k, columns=snap_%d) -> pk_<quantity>.h5 (power_spectrum_3d.py:228-249)."""

@@ -504,6 +504,39 @@ int ast_power_bin_1d(const void* spec1_d, const void* spec2_d, int dtype, int nm
                      double boxsize, int i0_start, int i0_count, int i1_start, int i1_count,
                      double* ksum_d, double* psum_d, long long* nmodes_d, int binning, void* stream);
 
+/* FFTPower(mode="2d", Nmu, los, poles): (k, mu) wedge sums and Legendre multipole sums over the same block of the
+ * half spectrum, with the line of sight along box axis `los` (0, 1 or 2).  nbodykit's published semantics restated
+ * (un-vendored: parity unpinned); nothing in the reference computes it (power_spectrum_3d.py:189 asks for "1d").
+ *   Lattice, k shell, dropped modes, Hermitian weight w and `binning`: exactly ast_power_bin_1d's; `binning` touches
+ *       the k shell only.  nb = nmesh/2-1 shells.
+ *   mu = |m_los| / |m|, folded onto [0, 1] (auto spectra, real part of cross spectra).  nmu (1 .. 1024) uniform bins,
+ *       left-closed, mu = 1 in the last.  Membership in exact integer arithmetic:
+ *       j = min(nmu - 1, max{ j : j^2 |m|^2 <= nmu^2 m_los^2 }) - a vector with mu exactly on an edge (3-4-5 triples:
+ *       mu = 3/5 at nmu = 5) opens the bin it sits on.  nbodykit digitizes a float64 mu; only such on-edge vectors
+ *       could land differently there.
+ *   ksum_d, musum_d (double) and nmodes_d (int64), (nb, nmu) each:  sum w |k|, sum w mu, sum w.  Data independent:
+ *       all three NULL skips them; spec1_d = psum_d = polesum_d = NULL computes only them.
+ *   psum_d (nb, nmu): sum w Re(d1 conj(d2)) L^3.
+ *   polesum_d (npoles, nb): row q = sum over ALL modes of the 1-D shell of w Re(d1 conj(d2)) L^3 L_l(mu), l = poles[q]
+ *       (host array; distinct even values from {0, 2, 4, 6, 8} - the folded spectrum holds no odd multipole), mu in
+ *       double, L_l by the three-term recurrence.  P_l = (2 l + 1) polesum / sum_shell w is left to the caller.
+ *   Everything is ACCUMULATED into caller-zeroed buffers, so partials over (i0, i1) blocks and ranks add.
+ *   The data pass sums in a workgroup's LDS table of (nb + 2)(nmu + npoles) doubles when that fits a CU's 160 KiB
+ *       (ast_power_bin_2d_lds_fits = 1), else straight into the global tables with fp64 atomics; the environment
+ *       variable ASTRILD_PK2D_LDS=0 forces the latter. */
+int ast_power_bin_2d_lds_fits(int nmesh, int nmu, int npoles);
+int ast_power_bin_2d(const void* spec1_d, const void* spec2_d, int dtype, int nmesh, double boxsize,
+                     int i0_start, int i0_count, int i1_start, int i1_count, int los, int nmu,
+                     const int* poles, int npoles, double* ksum_d, double* musum_d, long long* nmodes_d,
+                     double* psum_d, double* polesum_d, int binning, void* stream);
+/* Redshift-space positions: out = pos; out[:, los] += factor * vel[:, los], then ONE periodic wrap into [0, L)
+ * (>= L: - L; < 0: + L, and a sum that rounds up to L becomes 0 - the result never equals L).  (np, 3) interleaved,
+ * dtype AST_F32 / AST_F64, arithmetic in that dtype; factor 0.01 is TPCF's vel / 100 (particles/hutils/tpcf.py:74-97).
+ * A shift of more than a box length leaves the coordinate outside [0, L): the caller decides (device.rsd_shift
+ * raises).  out_d may alias pos_d. */
+int ast_rsd_shift(const void* pos_d, const void* vel_d, int dtype, size_t np, int los, double factor, double boxsize,
+                  void* out_d, void* stream);
+
 /* --------------------------------------------------- a-10: bispectrum */
 
 /* The reference's Bispectrum3D computes P(k) (bispectra/bispectrum_3d.py:165-215);
