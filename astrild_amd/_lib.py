@@ -178,6 +178,9 @@ SIGNATURES = {
     "ast_tunnels_workspace_bytes": (_sz, [_sz, _i]),
     "ast_tunnels_max_npix": (_i, []),
     "ast_tunnels_find": (_i, [_vp, _vp, _sz, _i, _i, _vp, _sz, _vp, _vp, _vp]),
+    "ast_grid_divergence": (_i, [_vp, _vp, _i, _sz, _sz, _sz, _d, _i, _i, _vp]),
+    "ast_vector_magnitude": (_i, [_vp, _vp, _i, _sz, _vp]),
+    "ast_spectral_divergence": (_i, [_vp, _vp, _vp, _vp, _i, _i, _d, _vp]),
 }
 
 _lib = None

@@ -1662,3 +1662,98 @@ def tunnels_circles(records, x_pix, y_pix):
     X, Y, W = rec[:, 4], rec[:, 5], rec[:, 6]
     ux, uy = X - W * x[rec[:, 0]], Y - W * y[rec[:, 0]]
     return X / W, Y / W, np.hypot(ux, uy) / W
+
+
+# ------------------------------------------------------------------ vector grids
+def check_divergence_args(shape, dtype, spacing):
+    """The argument checks of ``divergence``, host only: ``shape`` (n0, n1, n2, 3) with every side >= 3, ``dtype``
+    float32 or float64 (torch or numpy), ``spacing`` a positive finite number.  Returns ``(shape, spacing)`` as ints and
+    a float, or raises ValueError."""
+    shape = tuple(int(s) for s in shape)
+    if len(shape) != 4:
+        raise ValueError(f"a vector grid (n0, n1, n2, 3) is expected, got {len(shape)}D")
+    if shape[3] != 3:
+        raise ValueError(f"the last axis must hold 3 components, got {shape[3]}")
+    if min(shape[:3]) < 3:
+        raise ValueError(f"every side must be at least 3 cells (second-order edges), got {shape[:3]}")
+    try:
+        name = str(dtype)[6:] if str(dtype).startswith("torch.") else np.dtype(dtype).name
+    except TypeError:
+        name = str(dtype)
+    if name not in ("float32", "float64"):
+        raise ValueError(f"dtype must be float32 or float64, got {dtype}")
+    try:
+        h = float(spacing)
+    except (TypeError, ValueError):
+        raise ValueError(f"spacing must be a number, got {spacing!r}") from None
+    if not (h > 0.0 and np.isfinite(h)):
+        raise ValueError(f"spacing must be positive and finite, got {spacing!r}")
+    return shape, h
+
+
+def divergence(v, spacing, periodic=False, out=None):
+    """Finite-difference divergence of a vector grid ``(n0, n1, n2, 3)`` (MapTransform._compute_divergence,
+    map_transform.py:92-104): ``np.gradient(v[..., a], spacing, axis=a, edge_order=2)`` summed over a = 0, 1, 2 in that
+    order, bit for bit, as a device tensor ``(n0, n1, n2)`` of v's dtype.  ``periodic``: central differences with
+    wrapped indices in every cell instead of numpy's one-sided edges.  ``v``: numpy array or tensor, float32 or float64.
+    ASTRILD_DIVERGENCE_TILED=0 selects the one-work-item-per-cell kernel instead of the streaming one (same bits)."""
+    shape, h = check_divergence_args(v.shape, v.dtype, spacing)
+    t = as_device(v)
+    if out is None:
+        out = torch.empty(shape[:3], dtype=t.dtype, device=t.device)
+    assert out.is_cuda and out.is_contiguous() and out.dtype == t.dtype and tuple(out.shape) == shape[:3]
+    variant = 0 if os.environ.get("ASTRILD_DIVERGENCE_TILED", "1") == "0" else 1
+    check(_lib.lib().ast_grid_divergence(ptr(t), ptr(out), real_code(t), shape[0], shape[1], shape[2], h,
+                                         int(bool(periodic)), variant, stream()), "ast_grid_divergence")
+    return out
+
+
+def vector_magnitude(v, out=None):
+    """``sqrt(sum(square(v), axis=-1))`` of a ``(..., 3)`` array (PowerSpectrum3D._get_vector_magnitude,
+    power_spectrum_3d.py:155-162), the squares added left to right as numpy adds a last axis of length 3; a device
+    tensor of v's dtype without the last axis."""
+    if len(v.shape) < 1 or int(v.shape[-1]) != 3:
+        raise ValueError(f"the last axis must hold 3 components, got shape {tuple(v.shape)}")
+    t = as_device(v)
+    code = real_code(t)
+    if out is None:
+        out = torch.empty(tuple(t.shape[:-1]), dtype=t.dtype, device=t.device)
+    assert out.is_cuda and out.is_contiguous() and out.dtype == t.dtype and out.numel() * 3 == t.numel()
+    check(_lib.lib().ast_vector_magnitude(ptr(t), ptr(out), code, out.numel(), stream()), "ast_vector_magnitude")
+    return out
+
+
+def spectral_divergence(cx, cy, cz, nmesh, boxsize, out=None):
+    """``i (k0 cx + k1 cy + k2 cz)`` of three half spectra ``(n, n, n/2 + 1)`` in the layout of ``r2c``, with
+    k_a = (2 pi / boxsize) m_a and m_a = 0 on the Nyquist planes.  ``out`` may be ``cx``."""
+    n = int(nmesh)
+    shape = (n, n, n // 2 + 1)
+    code = _CPLX[cx.dtype]
+    for c in (cx, cy, cz):
+        assert c.is_cuda and c.is_contiguous() and c.dtype == cx.dtype and tuple(c.shape) == shape
+    if out is None:
+        out = torch.empty_like(cx)
+    assert out.is_cuda and out.is_contiguous() and out.dtype == cx.dtype and tuple(out.shape) == shape
+    check(_lib.lib().ast_spectral_divergence(ptr(cx), ptr(cy), ptr(cz), ptr(out), code, n, float(boxsize), stream()),
+          "ast_spectral_divergence")
+    return out
+
+
+def velocity_divergence_power(v, boxsize, binning=None):
+    """P_theta-theta(k) of a velocity grid ``(n, n, n, 3)``, theta = div v formed in Fourier space: each component is
+    transformed (``r2c``), ``spectral_divergence`` combines the three spectra, and the shells are binned as in
+    ``fftpower_1d``; the same dict and normalisation as ``fftpower_1d`` of the real-space theta grid, shotnoise 0.  A
+    float32 ``v`` is widened to double, as ``fftpower_1d`` does off its fused path: an fp32 transform would leave the
+    round-off of a component's O(1) mean on the low shells.
+
+    The finite-difference theta of ``divergence`` put through ``fftpower_1d`` is not the same spectrum: a central
+    difference of spacing h multiplies the term of axis a by sin(k_a h) / (k_a h), so its power falls below this one
+    towards the Nyquist frequency.  The spectral derivative carries no such factor."""
+    n = int(v.shape[0])
+    if tuple(v.shape) != (n, n, n, 3) or n % 2 != 0:
+        raise ValueError(f"a velocity grid (n, n, n, 3) with even n is expected, got shape {tuple(v.shape)}")
+    t = as_device(v)
+    real_code(t)
+    spectra = [r2c(t[..., a].to(torch.float64).contiguous()) for a in range(3)]
+    theta = spectral_divergence(*spectra, n, boxsize, out=spectra[0])
+    return finish_power(*power_bin_1d(theta, None, n, boxsize, binning=binning))

@@ -957,6 +957,30 @@ int ast_tunnels_max_npix(void);
 int ast_tunnels_find(const int* x_d, const int* y_d, size_t n, int npix, int single_cell, void* work_d,
                      size_t work_bytes, long long* records_d, unsigned long long* count_d, void* stream);
 
+/* ------------------------------------------------- vector grids */
+
+/* Finite-difference divergence of a vector grid: particles/hutils/map_transform.py:92-104 (_compute_divergence: three
+ * np.gradient(value_map[:, :, :, a], 1 / boxsize, axis=a, edge_order=2) calls and their sum).  v_d: a contiguous
+ * (n0, n1, n2, 3) array of dtype AST_F32 / AST_F64, axis 0 slowest, components interleaved; out_d: (n0, n1, n2) of the
+ * same dtype.  Every side >= 3, sides need not be equal.  With T the dtype and every constant rounded to T:
+ * interior cells, and all cells when periodic = 1 (indices wrap), d = (f[i+1] - f[i-1]) / T(2 h), a true division;
+ * periodic = 0: first cell (T(-1.5/h) f[0] + T(2/h) f[1]) + T(-0.5/h) f[2], last cell (T(0.5/h) f[n-3] +
+ * T(-2/h) f[n-2]) + T(1.5/h) f[n-1]; out = (d0(v_0) + d1(v_1)) + d2(v_2) - numpy's result bit for bit.  variant 0: one
+ * work item per cell, plain loads; variant 1: a workgroup marches a (y, z) tile along axis 0, rows fetched once with
+ * 16-byte accesses into LDS (an input that is not 16-byte aligned, or too many tiles for one launch, takes variant 0).
+ * Both give the same bits.  All indexing is 64-bit. */
+int ast_grid_divergence(const void* v_d, void* out_d, int dtype, size_t n0, size_t n1, size_t n2, double h,
+                        int periodic, int variant, void* stream);
+/* out[c] = sqrt((v[3c]^2 + v[3c+1]^2) + v[3c+2]^2), c < count: power_spectrum_3d.py:155-162 (_get_vector_magnitude,
+ * np.sqrt(np.sum(np.square(value_map), axis=3))). */
+int ast_vector_magnitude(const void* v_d, void* out_d, int dtype, size_t count, void* stream);
+/* Divergence in Fourier space of three contiguous half spectra (n, n, n/2 + 1) in the layout of ast_fft_tile_r2c_3d,
+ * complex64 (AST_F32) or complex128 (AST_F64): out = i ((k0 cx + k1 cy) + k2 cz), k_a = (2 pi / boxsize) m_a, m_a = j
+ * for j < n/2, j - n for j > n/2 and 0 at j = n/2 (an odd derivative of a real field has no Nyquist component).  out_d
+ * may be cx_d.  No reference counterpart (the reference differentiates in real space only). */
+int ast_spectral_divergence(const void* cx_d, const void* cy_d, const void* cz_d, void* out_d, int cdtype, int nmesh,
+                            double boxsize, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
