@@ -171,6 +171,9 @@ SIGNATURES = {
     "ast_tpcf_max_bins": (_i, []),
     "ast_tpcf_prepare": (_i, [_vp, _i, _vp, _i, _i, _d, _sz, _vp, _sz, _vp, _vp]),
     "ast_tpcf_pair_counts": (_i, [_vp, _sz, _sz, _d, _i, _vp, _i, _vp, _i, _i, _vp, _vp]),
+    "ast_tpcf_cross_workspace_bytes": (_sz, [_sz, _sz, _i, _i]),
+    "ast_tpcf_cross_prepare": (_i, [_vp, _i, _vp, _i, _sz, _vp, _i, _vp, _i, _sz, _i, _d, _vp, _sz, _vp, _vp]),
+    "ast_tpcf_cross_counts": (_i, [_vp, _sz, _sz, _sz, _i, _d, _i, _vp, _i, _vp, _i, _i, _vp, _vp]),
     "ast_profile2d_max_bins": (_i, []),
     "ast_profile2d_band_rows": (_i, []),
     "ast_profile2d_workspace_bytes": (_sz, [_sz, _sz, _i]),

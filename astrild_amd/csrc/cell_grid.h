@@ -1,9 +1,9 @@
 // Uniform cell grid shared by the pair finders (pairwise.hip, pairwise_pdf.hip, tpcf.hip): objects sorted by cell with a
 // counting sort (a count kernel -> grid_scan_kernel -> grid_scatter_kernel), and a work list of (tile of BLOCK objects of
 // a cell, one of the GRID_NEIGH half-shell neighbours) that a persistent pair kernel walks.  The grid_box_* part is the
-// non-periodic grid over the catalogue's bounding box (pairwise.hip, pairwise_pdf.hip); tpcf.hip plans its own periodic
-// one.  Everything here has internal linkage: each translation unit gets its own copy of the kernels and of the offset
-// table.
+// non-periodic grid over the catalogue's bounding box (pairwise.hip, pairwise_pdf.hip, and tpcf.hip for open
+// boundaries); tpcf.hip plans its own periodic one.  Everything here has internal linkage: each translation unit gets
+// its own copy of the kernels and of the offset table.
 #pragma once
 #include "ast_common.h"
 
@@ -114,13 +114,13 @@ struct GridBoxParams {
 
 inline size_t grid_box_cells_cap(size_t n) { return n < 1 ? 1 : (n < GRID_BOX_MAX_CELLS ? n : GRID_BOX_MAX_CELLS); }
 
-// One thread: the grid.  Cells are at least s = rmax (1 + 1e-6) wide per axis, plus a margin for the rounding
+// The grid, planned by one thread (grid_box_plan_kernel, or a caller's own plan kernel whose reach lives in device
+// memory).  Cells are at least s = rmax (1 + 1e-6) wide per axis, plus a margin for the rounding
 // of coordinates far from the origin, so a pair within reach lies in the same or an adjacent cell; at most `cap`
 // cells in all (wider cells past that).  single != 0: one cell.  (A template so that only the files that launch it
 // carry a copy.)
 template <typename Params>
-__global__ void grid_box_plan_kernel(Params* prm, double rmax, unsigned cap, int single) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+__device__ inline void grid_box_plan(Params* prm, double rmax, unsigned cap, int single) {
     double lo[3], ext[3], amax = 0.0;
     for (int a = 0; a < 3; ++a) {
         lo[a] = key2d(prm->kmin[a]);
@@ -150,6 +150,12 @@ __global__ void grid_box_plan_kernel(Params* prm, double rmax, unsigned cap, int
         prm->inv_cs[a] = dims[a] > 1 ? (double)dims[a] / ext[a] : 0.0;
     }
     prm->ncells = (unsigned)dims[0] * (unsigned)dims[1] * (unsigned)dims[2];
+}
+
+template <typename Params>
+__global__ void grid_box_plan_kernel(Params* prm, double rmax, unsigned cap, int single) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    grid_box_plan(prm, rmax, cap, single);
 }
 
 template <typename Obj>

@@ -1,4 +1,5 @@
-// Two-point correlation function of a periodic box (particles/hutils/tpcf.py, halotools' s_mu_tpcf / tpcf): per-object
+// Two-point correlation function (particles/hutils/tpcf.py, halotools' s_mu_tpcf / tpcf), first of one sample in a
+// periodic box, then (second half of the file) of two samples in a periodic box or with open boundaries: per-object
 // prep (redshift-space shift, wrap, bounds), a periodic uniform cell grid (counting sort by cell, cell_grid.h) as the
 // pair finder, a tiled pair kernel that counts minimum-image pairs into an exact integer (s, mu) histogram in LDS, and a
 // fixed-order sum of the workgroup rows.  All pair arithmetic is fp64 (the library is built with -ffp-contract=off).
@@ -393,6 +394,334 @@ extern "C" int ast_tpcf_pair_counts(void* work_d, size_t work_bytes, size_t n, d
     }
     {
         AST_PROF("tpcf_reduce", s);
+        tp_reduce_kernel<<<(nbins + 255) / 256, 256, 0, s>>>(part, nbins, counts_d);
+        AST_CHECK_LAUNCH();
+    }
+    return AST_OK;
+}
+
+// ---- two sets, periodic cube or open boundaries (ast_tpcf_cross_prepare / ast_tpcf_cross_counts)
+namespace {
+
+constexpr int TPX_NEIGH = 27;               // cross pairs: the cell itself and all 26 neighbours
+
+inline size_t tpx_cells_cap(size_t n1, size_t n2) { return cells_cap(n1 > n2 ? n1 : n2); }
+
+// One grid (GridBoxParams) shared by both sets; per set its own bounds (TpParams, only kmin / kmax used), counts,
+// cell starts, cell numbers, fp64 objects and their cell-sorted copy.  Only set 1 has tiles; tile_start[1] is where
+// the scan of set 2 puts the tile list nobody reads.  Everything before `part` is independent of the bin counts.
+struct TpxLayout {
+    size_t grid, set_prm[2], cnt[2], cell_start[2], tile_start[2], cursor, cell_of[2], obj[2], sorted[2], part, total;
+    TpxLayout(size_t n1, size_t n2, int nbins) {
+        const size_t cap = tpx_cells_cap(n1, n2);
+        const size_t n[2] = {n1, n2};
+        size_t o = 0;
+        grid = o; o += align256(sizeof(GridBoxParams));
+        for (int s = 0; s < 2; ++s) {
+            set_prm[s] = o;    o += align256(sizeof(TpParams));
+            cnt[s] = o;        o += align256(cap * 4);
+            cell_start[s] = o; o += align256((cap + 1) * 4);
+            tile_start[s] = o; o += align256((cap + 1) * 4);
+            cell_of[s] = o;    o += align256(n[s] * 4);
+            obj[s] = o;        o += align256(n[s] * sizeof(TpObj));
+            sorted[s] = o;     o += align256(n[s] * sizeof(TpObj));
+        }
+        cursor = o; o += align256(cap * 4);
+        part = o;   o += align256((size_t)TP_GRID * (size_t)nbins * 8);
+        total = o;
+    }
+};
+
+// bounds[6 s + 0..2] = min, bounds[6 s + 3..5] = max of set s (as tp_bounds_kernel); the union of both boxes goes to
+// the shared grid's kmin / kmax (an empty set leaves the other's box; both empty: kmin > kmax, and nothing is planned).
+__global__ void tpx_bounds_kernel(const TpParams* prm1, const TpParams* prm2, GridBoxParams* grid,
+                                  double* __restrict__ bounds) {
+    const int a = threadIdx.x;
+    if (a >= 3) return;
+    const TpParams* prm[2] = {prm1, prm2};
+    unsigned long long umn = ~0ull, umx = 0ull;
+    for (int s = 0; s < 2; ++s) {
+        const unsigned long long kmn = prm[s]->kmin[a], kmx = prm[s]->kmax[a];
+        bounds[6 * s + a] = kmn > kmx ? INFINITY : key2d(kmn);
+        bounds[6 * s + 3 + a] = kmn > kmx ? -INFINITY : key2d(kmx);
+        umn = kmn < umn ? kmn : umn;
+        umx = kmx > umx ? kmx : umx;
+    }
+    grid->kmin[a] = umn;
+    grid->kmax[a] = umx;
+}
+
+// One thread: the shared grid.  boxsize > 0: tp_plan_kernel's periodic plan (dims cells per axis from the origin,
+// >= 3 or one cell); boxsize == 0: grid_box_plan over the union bounding box, per-axis dims that may be 1.
+__global__ void tpx_plan_kernel(GridBoxParams* prm, const double* __restrict__ s_edges, int ns, double boxsize,
+                                unsigned cap, int single) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    if (!(boxsize > 0.0)) {
+        grid_box_plan(prm, s_edges[ns], cap, single);
+        return;
+    }
+    int d = 1;
+    const double m = floor(boxsize / (s_edges[ns] * (1.0 + 1e-6)));
+    if (!single && m >= 3.0) {
+        d = m > 1024.0 ? 1024 : (int)m;
+        while ((unsigned long long)d * d * d > cap) --d;
+    }
+    for (int a = 0; a < 3; ++a) {
+        prm->lo[a] = 0.0;
+        prm->dims[a] = d;
+        prm->inv_cs[a] = d > 1 ? (double)d / boxsize : 0.0;
+    }
+    prm->ncells = (unsigned)(d * d * d);
+}
+
+// tp_pair_kernel for two sets.  Work item = (tile of TP_BLOCK set-1 objects of cell a, neighbour k); the j objects are
+// those of set 2 in cell a + offset[k], staged through LDS TP_BLOCK at a time.
+//   auto_pairs == 0: k over all 27 offsets, every (i, j) once.
+//   auto_pairs != 0: sorted2 / cell_start2 are set 1's own; k over the 14 half-shell offsets, j > i at k = 0.
+//   boxsize > 0: minimum image, neighbours wrap (dims >= 3 on every axis, or one cell: offset 0 only).
+//   boxsize == 0: a = |dx|, a neighbour outside [0, dims) on any axis is skipped.
+// Bins, LDS counters, flushes and the workgroup rows are tp_pair_kernel's.
+__global__ void __launch_bounds__(TP_BLOCK)
+tpx_pair_kernel(const TpObj* __restrict__ sorted1, const unsigned* __restrict__ cell_start1,
+                const unsigned* __restrict__ tile_start, const TpObj* __restrict__ sorted2,
+                const unsigned* __restrict__ cell_start2, const GridBoxParams* prm, double boxsize, int auto_pairs,
+                int los, const double* __restrict__ s_edges, int ns, const double* __restrict__ mu_edges, int nmu,
+                int hcopies, unsigned long long flush_at, unsigned long long* __restrict__ part) {
+    extern __shared__ double lds[];
+    double* jr = lds;                                   // [3][TP_BLOCK]: the staged j objects
+    double* s2 = jr + 3 * TP_BLOCK;                     // [ns + 1] squared s edges
+    double* me = s2 + (ns + 1);                         // [nmu + 1] mu edges
+    unsigned* hist = (unsigned*)(me + (nmu + 1));       // [hcopies][nbins]
+    const int tid = threadIdx.x, w = tid / 64;
+    const int nbins = ns * (nmu > 0 ? nmu : 1);
+    for (int k = tid; k <= ns; k += TP_BLOCK) s2[k] = s_edges[k] * s_edges[k];
+    for (int k = tid; k <= nmu && nmu > 0; k += TP_BLOCK) me[k] = mu_edges[k];
+    for (int k = tid; k < hcopies * nbins; k += TP_BLOCK) hist[k] = 0u;
+    unsigned* whist = hist + (w % hcopies) * nbins;
+    unsigned long long* row = part + (size_t)blockIdx.x * nbins;
+    bool flushed = false;                               // row holds a partial sum (else it is not yet written)
+    unsigned long long pending = 0;                     // bound on the pairs added to any counter since the last flush
+
+    auto flush = [&]() {
+        __syncthreads();
+        for (int b = tid; b < nbins; b += TP_BLOCK) {
+            unsigned long long sum = 0;
+            for (int c = 0; c < hcopies; ++c) { sum += hist[c * nbins + b]; hist[c * nbins + b] = 0u; }
+            row[b] = flushed ? row[b] + sum : sum;
+        }
+        flushed = true;
+        pending = 0;
+        __syncthreads();
+    };
+
+    const bool periodic = boxsize > 0.0;
+    const int dims[3] = {prm->dims[0], prm->dims[1], prm->dims[2]};
+    const unsigned ncells = prm->ncells;
+    const int nneigh = auto_pairs ? GRID_NEIGH : TPX_NEIGH;
+    const unsigned long long nitems = (unsigned long long)prm->ntiles * (unsigned long long)nneigh;
+    __syncthreads();
+    const double s2lo = s2[0], s2hi = s2[ns];
+    const double mulo = nmu > 0 ? me[0] : 0.0, muhi = nmu > 0 ? me[nmu] : 0.0;
+    for (unsigned long long item = blockIdx.x; item < nitems; item += gridDim.x) {
+        const unsigned tile = (unsigned)(item / (unsigned)nneigh);
+        const int k = (int)(item % (unsigned)nneigh);
+        int off[3];
+        if (auto_pairs) {
+            for (int c = 0; c < 3; ++c) off[c] = grid_offsets[k][c];
+        } else {
+            off[0] = k % 3 - 1; off[1] = (k / 3) % 3 - 1; off[2] = k / 9 - 1;
+        }
+        const unsigned a = grid_cell_of_tile(tile_start, ncells, tile);
+        const int ac[3] = {(int)(a % (unsigned)dims[0]), (int)((a / (unsigned)dims[0]) % (unsigned)dims[1]),
+                           (int)(a / ((unsigned)dims[0] * (unsigned)dims[1]))};
+        int bc[3];
+        bool skip = false;
+        for (int c = 0; c < 3; ++c) {
+            int v = ac[c] + off[c];
+            if (periodic && dims[c] >= 3) v = (v + dims[c]) % dims[c];
+            else if (v < 0 || v >= dims[c]) skip = true;    // open boundary, or the one cell of a periodic box
+            bc[c] = v;
+        }
+        if (skip) continue;
+        const unsigned b = ((unsigned)bc[2] * (unsigned)dims[1] + (unsigned)bc[1]) * (unsigned)dims[0] + (unsigned)bc[0];
+        const bool self = auto_pairs && k == 0;
+        const unsigned i0 = cell_start1[a] + (tile - tile_start[a]) * TP_BLOCK;
+        const unsigned i1 = min(i0 + TP_BLOCK, cell_start1[a + 1]);
+        const unsigned j0 = self ? i0 + 1 : cell_start2[b];
+        const unsigned j1 = cell_start2[b + 1];
+        if (j0 >= j1) continue;
+
+        const unsigned i = i0 + tid;
+        const bool valid = i < i1;
+        TpObj oi;
+        if (valid) oi = sorted1[i];
+        for (unsigned jc = j0; jc < j1; jc += TP_BLOCK) {
+            const int m = (int)min((unsigned)TP_BLOCK, j1 - jc);
+            const unsigned long long stage = (unsigned long long)(i1 - i0) * (unsigned long long)m;
+            if (pending + stage > flush_at) flush();
+            pending += stage;
+            __syncthreads();
+            if (jc + tid < j1) {
+                const TpObj oj = sorted2[jc + tid];
+                for (int c = 0; c < 3; ++c) jr[c * TP_BLOCK + tid] = oj.r[c];
+            }
+            __syncthreads();
+            if (!valid) continue;
+            const int q0 = (self && i + 1 > jc) ? (int)min((unsigned)m, i + 1 - jc) : 0;
+            for (int q = q0; q < m; ++q) {
+                double px = fabs(oi.r[0] - jr[q]), py = fabs(oi.r[1] - jr[TP_BLOCK + q]),
+                       pz = fabs(oi.r[2] - jr[2 * TP_BLOCK + q]);
+                if (periodic) {
+                    px = fmin(px, boxsize - px);
+                    py = fmin(py, boxsize - py);
+                    pz = fmin(pz, boxsize - pz);
+                }
+                const double d2 = (px * px + py * py) + pz * pz;
+                if (!(d2 <= s2hi) || !(d2 > s2lo)) continue;
+                int lo = 0, hi = ns;                    // s2[lo] < d2 <= s2[hi]
+                while (hi - lo > 1) {
+                    const int mid = (lo + hi) >> 1;
+                    if (d2 <= s2[mid]) hi = mid; else lo = mid;
+                }
+                int bin = lo;
+                if (nmu > 0) {
+                    const double alos = los == 0 ? px : (los == 1 ? py : pz);
+                    const double mu = alos / sqrt(d2);
+                    if (!(mu > mulo) || !(mu <= muhi)) continue;
+                    int ml = 0, mh = nmu;               // me[ml] < mu <= me[mh]
+                    while (mh - ml > 1) {
+                        const int mid = (ml + mh) >> 1;
+                        if (mu <= me[mid]) mh = mid; else ml = mid;
+                    }
+                    bin = lo * nmu + ml;
+                }
+                atomicAdd(&whist[bin], 1u);
+            }
+        }
+    }
+    flush();
+}
+
+int tpx_prep(const void* pos, int pos_dtype, const void* vel, int vel_dtype, int los, double boxsize, size_t n,
+             TpObj* obj, TpParams* prm, hipStream_t s) {
+    AST_CHECK_HIP(hipMemsetAsync(prm->kmin, 0xff, sizeof(prm->kmin), s));
+    AST_CHECK_HIP(hipMemsetAsync(prm->kmax, 0x00, sizeof(prm->kmax), s));
+    if (n == 0) return AST_OK;
+    const bool v32 = vel && vel_dtype == AST_F32;
+    if (pos_dtype == AST_F32 && v32)
+        launch_prep<float, float>(pos, vel, los, boxsize, n, obj, prm, s);
+    else if (pos_dtype == AST_F32)
+        launch_prep<float, double>(pos, vel, los, boxsize, n, obj, prm, s);
+    else if (v32)
+        launch_prep<double, float>(pos, vel, los, boxsize, n, obj, prm, s);
+    else
+        launch_prep<double, double>(pos, vel, los, boxsize, n, obj, prm, s);
+    AST_CHECK_LAUNCH();
+    return AST_OK;
+}
+
+}  // namespace
+
+extern "C" size_t ast_tpcf_cross_workspace_bytes(size_t n1, size_t n2, int ns, int nmu) {
+    if (!bins_ok(ns, nmu)) return 0;
+    return TpxLayout(n1, n2, nbins_of(ns, nmu)).total;
+}
+
+extern "C" int ast_tpcf_cross_prepare(const void* pos1_d, int pos1_dtype, const void* vel1_d, int vel1_dtype,
+                                      size_t n1, const void* pos2_d, int pos2_dtype, const void* vel2_d,
+                                      int vel2_dtype, size_t n2, int los, double boxsize, void* work_d,
+                                      size_t work_bytes, double* bounds_d, void* stream) {
+    AST_CHECK_ARG(n1 == 0 || pos1_dtype == AST_F32 || pos1_dtype == AST_F64);
+    AST_CHECK_ARG(n2 == 0 || pos2_dtype == AST_F32 || pos2_dtype == AST_F64);
+    AST_CHECK_ARG(vel1_d == nullptr || vel1_dtype == AST_F32 || vel1_dtype == AST_F64);
+    AST_CHECK_ARG(vel2_d == nullptr || vel2_dtype == AST_F32 || vel2_dtype == AST_F64);
+    AST_CHECK_ARG(los >= 0 && los <= 2);
+    AST_CHECK_ARG(boxsize >= 0.0 && std::isfinite(boxsize));
+    AST_CHECK_ARG(n1 < (size_t(1) << 31) && n2 < (size_t(1) << 31));
+    AST_CHECK_ARG((n1 == 0 || pos1_d) && (n2 == 0 || pos2_d));
+    AST_CHECK_ARG(bounds_d);
+    const TpxLayout L(n1, n2, 1);
+    AST_CHECK_ARG(work_d && work_bytes >= L.part);
+    hipStream_t s = ast::as_stream(stream);
+    char* ws = (char*)work_d;
+    TpParams* prm1 = (TpParams*)(ws + L.set_prm[0]);
+    TpParams* prm2 = (TpParams*)(ws + L.set_prm[1]);
+    {
+        // boxsize == 0 (open): tp_prep_kernel's wrap subtracts or adds 0, which changes nothing
+        AST_PROF("tpcf_cross_prep", s);
+        int rc = tpx_prep(pos1_d, pos1_dtype, vel1_d, vel1_dtype, los, boxsize, n1, (TpObj*)(ws + L.obj[0]), prm1, s);
+        if (rc != AST_OK) return rc;
+        rc = tpx_prep(pos2_d, pos2_dtype, vel2_d, vel2_dtype, los, boxsize, n2, (TpObj*)(ws + L.obj[1]), prm2, s);
+        if (rc != AST_OK) return rc;
+    }
+    tpx_bounds_kernel<<<1, 64, 0, s>>>(prm1, prm2, (GridBoxParams*)(ws + L.grid), bounds_d);
+    AST_CHECK_LAUNCH();
+    return AST_OK;
+}
+
+extern "C" int ast_tpcf_cross_counts(void* work_d, size_t work_bytes, size_t n1, size_t n2, int auto_pairs,
+                                     double boxsize, int los, const double* s_edges_d, int ns,
+                                     const double* mu_edges_d, int nmu, int single_cell,
+                                     unsigned long long* counts_d, void* stream) {
+    AST_CHECK_ARG(bins_ok(ns, nmu));
+    AST_CHECK_ARG(los >= 0 && los <= 2);
+    AST_CHECK_ARG(boxsize >= 0.0 && std::isfinite(boxsize));
+    AST_CHECK_ARG(n1 < (size_t(1) << 31) && n2 < (size_t(1) << 31));
+    AST_CHECK_ARG(s_edges_d && (nmu == 0 || mu_edges_d) && counts_d);
+    AST_CHECK_ARG(work_d && work_bytes >= ast_tpcf_cross_workspace_bytes(n1, n2, ns, nmu));
+    hipStream_t s = ast::as_stream(stream);
+    const int nbins = nbins_of(ns, nmu);
+    if (auto_pairs ? n1 < 2 : (n1 == 0 || n2 == 0)) {
+        AST_CHECK_HIP(hipMemsetAsync(counts_d, 0, nbins * sizeof(unsigned long long), s));
+        return AST_OK;
+    }
+    const TpxLayout L(n1, n2, nbins);
+    char* ws = (char*)work_d;
+    GridBoxParams* prm = (GridBoxParams*)(ws + L.grid);
+    unsigned* cursor = (unsigned*)(ws + L.cursor);
+    unsigned long long* part = (unsigned long long*)(ws + L.part);
+    const size_t cap = tpx_cells_cap(n1, n2);
+    const size_t n[2] = {n1, n2};
+    {
+        AST_PROF("tpcf_cross_grid", s);
+        tpx_plan_kernel<<<1, 64, 0, s>>>(prm, s_edges_d, ns, boxsize, (unsigned)cap, single_cell);
+        AST_CHECK_LAUNCH();
+        // set 2 first: the scan of set 1 then leaves its tile count in prm->ntiles
+        for (int q = auto_pairs ? 0 : 1; q >= 0; --q) {
+            unsigned* cnt = (unsigned*)(ws + L.cnt[q]);
+            unsigned* cell_of = (unsigned*)(ws + L.cell_of[q]);
+            const TpObj* obj = (const TpObj*)(ws + L.obj[q]);
+            AST_CHECK_HIP(hipMemsetAsync(cnt, 0, cap * 4, s));
+            grid_box_count_kernel<<<ast::stream_grid(n[q], 256), 256, 0, s>>>(obj, n[q], prm, cell_of, cnt);
+            AST_CHECK_LAUNCH();
+            grid_scan_kernel<TP_BLOCK><<<1, 1024, 0, s>>>(cnt, prm, (unsigned*)(ws + L.cell_start[q]),
+                                                          (unsigned*)(ws + L.tile_start[q]), cursor);
+            AST_CHECK_LAUNCH();
+            grid_scatter_kernel<<<ast::stream_grid(n[q], 256), 256, 0, s>>>(obj, n[q], cell_of, cursor,
+                                                                             (TpObj*)(ws + L.sorted[q]));
+            AST_CHECK_LAUNCH();
+        }
+    }
+    const int q2 = auto_pairs ? 0 : 1;
+    const size_t fixed = (size_t)3 * TP_BLOCK * sizeof(double) + (size_t)(ns + 1 + nmu + 1) * sizeof(double);
+    int hcopies = TP_WAVES;
+    while (hcopies > 1 && fixed + (size_t)hcopies * nbins * 4 > TP_LDS) hcopies /= 2;
+    const size_t lds = fixed + (size_t)hcopies * nbins * 4;
+    AST_CHECK_ARG(lds <= TP_LDS);
+    unsigned long long flush_at = TP_FLUSH_AT;
+    if (const char* f = getenv("AST_TPCF_FLUSH_AT")) flush_at = strtoull(f, nullptr, 10);
+    if (flush_at > TP_FLUSH_AT) flush_at = TP_FLUSH_AT;
+    {
+        AST_PROF("tpcf_cross_pairs", s);
+        tpx_pair_kernel<<<TP_GRID, TP_BLOCK, lds, s>>>(
+            (const TpObj*)(ws + L.sorted[0]), (const unsigned*)(ws + L.cell_start[0]),
+            (const unsigned*)(ws + L.tile_start[0]), (const TpObj*)(ws + L.sorted[q2]),
+            (const unsigned*)(ws + L.cell_start[q2]), prm, boxsize, auto_pairs, los, s_edges_d, ns, mu_edges_d, nmu,
+            hcopies, flush_at, part);
+        AST_CHECK_LAUNCH();
+    }
+    {
+        AST_PROF("tpcf_cross_reduce", s);
         tp_reduce_kernel<<<(nbins + 255) / 256, 256, 0, s>>>(part, nbins, counts_d);
         AST_CHECK_LAUNCH();
     }

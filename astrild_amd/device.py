@@ -1467,17 +1467,19 @@ def pairwise_velocity_pdf(pos, vel, r, dist_bin, vel_bin, kind, dist_width=1.0, 
 
 
 # ------------------------------------------------------------------ two-point correlation function
-def check_tpcf_edges(s_edges, mu_edges, boxsize):
+def check_tpcf_edges(s_edges, mu_edges, boxsize, periodic=True):
     """halotools' argument checks of a periodic (s, mu) pair count, on the host: fp64 edges ``(s, mu)`` (``mu`` None
     stays None) or ValueError.  s edges strictly increasing, >= 0, max < boxsize / 3; mu edges strictly increasing
-    within [0, 1]; at most ``ast_tpcf_max_bins()`` bins."""
-    boxsize = float(boxsize)
-    if not (np.isfinite(boxsize) and boxsize > 0):
-        raise ValueError(f"boxsize must be positive and finite, got {boxsize}")
+    within [0, 1]; at most ``ast_tpcf_max_bins()`` bins.  ``periodic=False`` (open boundaries): ``boxsize`` is not
+    looked at and the top s edge is free."""
+    if periodic:
+        boxsize = float(boxsize)
+        if not (np.isfinite(boxsize) and boxsize > 0):
+            raise ValueError(f"boxsize must be positive and finite, got {boxsize}")
     s = np.asarray(s_edges, dtype=np.float64).reshape(-1)
     if len(s) < 2 or not np.all(np.isfinite(s)) or np.any(np.diff(s) <= 0) or s[0] < 0:
         raise ValueError("s edges must be at least two finite, non-negative, strictly increasing values")
-    if not s[-1] < boxsize / 3.0:
+    if periodic and not s[-1] < boxsize / 3.0:
         raise ValueError(f"the largest s edge ({s[-1]}) must be below boxsize / 3 ({boxsize / 3.0})")
     mu = None
     if mu_edges is not None:
@@ -1532,6 +1534,71 @@ def tpcf_pair_counts(pos, boxsize, s_edges, mu_edges=None, vel=None, los=2):
     counts = torch.empty((ns, nmu) if nmu else (ns,), dtype=torch.int64, device=p.device)
     check(lib.ast_tpcf_pair_counts(ptr(work), ws_bytes, n, boxsize, los, ptr(s_d), ns, ptr(mu_d), nmu, int(single),
                                    ptr(counts), st), "ast_tpcf_pair_counts")
+    return counts
+
+
+def _tpcf_set(pos, vel, name):
+    """(N, 3) positions and optional velocities of one sample as real device tensors, or ValueError."""
+    p = as_device(pos)
+    p = p if p.dtype in _REAL else p.to(torch.float64)
+    n = p.shape[0] if p.dim() == 2 else -1
+    if p.shape != (n, 3):
+        raise ValueError(f"{name} must be (N, 3), got {tuple(p.shape)}")
+    v = None
+    if vel is not None:
+        v = as_device(vel)
+        v = v if v.dtype in _REAL else v.to(torch.float64)
+        if v.shape != (n, 3):
+            raise ValueError(f"the velocities of {name} must be (N, 3) like it, got {tuple(v.shape)}")
+    return p, v, n
+
+
+def tpcf_cross_counts(pos1, pos2, s_edges, mu_edges=None, boxsize=None, vel1=None, vel2=None, los=2):
+    """Pair counts between two samples for the two-point correlation function (ast_tpcf_cross_prepare /
+    ast_tpcf_cross_counts): an int64 device tensor, (ns, nmu) with ``mu_edges``, else (ns,), of every pair (i of
+    ``pos1``, j of ``pos2``); ``pos2=None``: the unordered pairs i < j of ``pos1``.  ``boxsize`` given: a periodic
+    cube, minimum image per axis, as tpcf_pair_counts; ``boxsize=None``: open boundaries, plain separations.
+    ``vel1`` / ``vel2``: the redshift-space shift pos[:, los] += vel[:, los] / 100 per sample in its own dtypes, with
+    the single wrap only when periodic.  Bins as tpcf_pair_counts; a pair at distance 0 never counts.  ValueError
+    (before any pair work) for bad edges (the top s edge is bounded by boxsize / 3 only when periodic), shapes or
+    ``los``, and from the device bounds: periodic, shifted coordinates outside [0, boxsize]; open, any non-finite
+    coordinate.  ASTRILD_TPCF_CELLS=0 forces one cell (all pairs) instead of the cell grid."""
+    import os
+    periodic = boxsize is not None
+    s, mu = check_tpcf_edges(s_edges, mu_edges, boxsize, periodic=periodic)
+    if los not in (0, 1, 2):
+        raise ValueError(f"los must be 0, 1 or 2, got {los}")
+    box = float(boxsize) if periodic else 0.0
+    lib = _lib.lib()
+    auto = pos2 is None
+    if auto and vel2 is not None:
+        raise ValueError("vel2 given without pos2")
+    p1, v1, n1 = _tpcf_set(pos1, vel1, "pos1")
+    p2, v2, n2 = (None, None, 0) if auto else _tpcf_set(pos2, vel2, "pos2")
+    ns, nmu = len(s) - 1, 0 if mu is None else len(mu) - 1
+    single = os.environ.get("ASTRILD_TPCF_CELLS", "1") == "0"
+    ws_bytes = lib.ast_tpcf_cross_workspace_bytes(n1, n2, ns, nmu)
+    work = torch.empty(ws_bytes, dtype=torch.uint8, device=p1.device)
+    bounds = torch.empty(12, dtype=torch.float64, device=p1.device)
+    st = stream()
+    code = lambda t: real_code(t) if t is not None else F64
+    check(lib.ast_tpcf_cross_prepare(ptr(p1), code(p1), ptr(v1), code(v1), n1, ptr(p2), code(p2), ptr(v2), code(v2), n2,
+                                     los, box, ptr(work), ws_bytes, ptr(bounds), st), "ast_tpcf_cross_prepare")
+    b = to_numpy(bounds).reshape(2, 6)
+    for k, n in enumerate((n1, n2)):
+        if not n:
+            continue
+        if periodic and not (np.all(b[k, :3] >= 0.0) and np.all(b[k, 3:] <= box)):
+            raise ValueError(f"positions of sample {k + 1} (after the redshift-space shift) must lie in [0, {box}]: "
+                             f"min {b[k, :3].tolist()}, max {b[k, 3:].tolist()}")
+        if not periodic and not np.all(np.isfinite(b[k])):
+            raise ValueError(f"positions of sample {k + 1} (after the redshift-space shift) must be finite: "
+                             f"min {b[k, :3].tolist()}, max {b[k, 3:].tolist()}")
+    s_d = as_device(s)
+    mu_d = as_device(mu) if mu is not None else None
+    counts = torch.empty((ns, nmu) if nmu else (ns,), dtype=torch.int64, device=p1.device)
+    check(lib.ast_tpcf_cross_counts(ptr(work), ws_bytes, n1, n2, int(auto), box, los, ptr(s_d), ns, ptr(mu_d), nmu,
+                                    int(single), ptr(counts), st), "ast_tpcf_cross_counts")
     return counts
 
 

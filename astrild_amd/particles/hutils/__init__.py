@@ -1,5 +1,5 @@
 from .stats_subfind import SubFind  # noqa: F401
 from .mean_pairwise_velocity import (make_rsep, make_rsep_uneven_bins, mean_pv_from_tv, mean_pv_radial,  # noqa: F401
                                      mean_pv_z_sign)
-from .tpcf import TPCF, tpcf_multipole, tpcf_r  # noqa: F401
+from .tpcf import TPCF, s_mu_tpcf, tpcf_multipole, tpcf_r  # noqa: F401
 from .map_transform import MapTransform, MapTransformWarning  # noqa: F401

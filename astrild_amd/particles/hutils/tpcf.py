@@ -1,5 +1,5 @@
-"""Two-point correlation function of a periodic box with astrild's API (src/astrild/particles/hutils/tpcf.py), the pair
-counts on the GPU.  The reference hands the work to halotools (``s_mu_tpcf``, and ``tpcf`` / ``tpcf_multipole`` in its
+"""Two-point correlation functions with astrild's API (src/astrild/particles/hutils/tpcf.py): one or two samples, in a
+periodic box with analytic or user randoms, or with open boundaries and user randoms; the pair counts on the GPU. The reference hands the work to halotools (``s_mu_tpcf``, and ``tpcf`` / ``tpcf_multipole`` in its
 commented-out halo code); halotools is not used here, and this module restates its behaviour as far as its published
 source fixes it, without a check against the library itself:
 
@@ -24,7 +24,37 @@ source fixes it, without a check against the library itself:
   Landy-Szalay) reduces to ``xi = DD / RR - 1``; all five names are accepted, anything else is a ``ValueError``.
   This arithmetic runs on the host in fp64 from the int64 counts.
 
-``nthreads`` is accepted and ignored.  Cross-correlations, user randoms and non-periodic samples are not supported.
+* **Two samples** (``sample2=`` of ``tpcf_r`` / ``s_mu_tpcf``, ``pos2=`` / ``vel2=`` of ``TPCF``; the reference's
+  halo code splits a catalogue at a mass threshold and correlates the halves this way, ``stats_subfind.py:155-218``):
+  as halotools returns them, ``xi_11`` without a second sample; with one, ``(xi_11, xi_12, xi_22)``, or ``xi_12``
+  alone with ``do_auto=False``, or ``(xi_11, xi_22)`` with ``do_cross=False``; both flags false is a ``ValueError``.
+  The cross counts ``D1D2`` are all pairs (i of sample 1, j of sample 2), with the geometry and bins above; coincident
+  points of the two samples (d = 0) never count.  In ``TPCF`` sample 2 is shifted and wrapped like sample 1.
+* **Analytic randoms with two samples** (``period`` given, no ``randoms``): the auto terms are the one-sample path
+  above, unchanged; the cross term is ``D1D2 / (N1 N2 v / L^3) - 1`` with ``v`` the shell volume times ``dmu``, for
+  every estimator name.
+* **User randoms** (``randoms=``; they have no velocities and are never shifted): with ``period`` every term is counted
+  with the minimum image, with ``period=None`` every term with open boundaries (plain separations; every coordinate
+  must be finite, and the top s edge is not bounded by a box).  ``period=None`` without ``randoms`` is a ``ValueError``.
+  The estimators, halotools' ``_TP_estimator`` as recalled from its source and not checked against the library: with
+  ``DD`` the ordered data pairs (2 x the unordered counts for an auto term, all pairs for the cross term),
+  ``RR`` = 2 x the unordered random pairs, ``DR`` all data-random pairs and ``Na, Nb, NR`` the sample sizes,
+
+  - Natural: ``NR NR / (Na Nb) DD / RR - 1``
+  - Davis-Peebles: ``NR / Nb DD / DR - 1``
+  - Hewett: ``NR NR / (Na Nb) DD / RR - NR / Na DR / RR``
+  - Hamilton: ``DD RR / (DR DR) - 1``
+  - Landy-Szalay: ``NR NR / (Na Nb) DD / RR - NR / Na 2 DR / RR + 1``
+
+  The auto terms use (a, b) = (1, 1) or (2, 2) with their own ``DaR``; the cross term uses (1, 2) with ``D1R`` only,
+  as halotools is recalled to do.  The symmetric cross Landy-Szalay, ``(D1D2 - D1R - D2R + RR) / RR`` with each count
+  normalised by its number of pairs, can be formed from ``return_counts``.  Host fp64 arithmetic from the int64 counts;
+  an empty ``RR`` or ``DR`` bin gives inf / nan as numpy does, not an exception.
+* **``return_counts``**: with a second sample or randoms (and always in ``s_mu_tpcf``) a dict of the raw int64 counts
+  that were needed, under ``D1D1, D1D2, D2D2, D1R, D2R, RR`` (unordered pairs for ``D1D1, D2D2, RR``); otherwise, as
+  before, the array of unordered ``D1D1`` counts.
+
+``nthreads`` is accepted and ignored.
 """
 from typing import Optional, Union
 
@@ -54,6 +84,98 @@ def _counts(pos, boxsize, s_edges, mu_edges, vel, los):
     return dev.to_numpy(dev.tpcf_pair_counts(pos, boxsize, s_edges, mu_edges=mu_edges, vel=vel, los=los))
 
 
+def _cross(pos1, pos2, boxsize, s_edges, mu_edges, vel1=None, vel2=None, los=2):
+    from ... import device as dev
+    return dev.to_numpy(dev.tpcf_cross_counts(pos1, pos2, s_edges, mu_edges=mu_edges, boxsize=boxsize, vel1=vel1,
+                                              vel2=vel2, los=los))
+
+
+def _estimate(estimator, dd, dr, rr, na, nb, nr):
+    """halotools' ``_TP_estimator`` from ordered pair counts (module docstring); ``dr`` / ``rr`` None when the
+    estimator does not use them."""
+    na, nb, nr = float(na), float(nb), float(nr)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        if estimator == "Natural":
+            return (nr * nr) / (na * nb) * dd / rr - 1.0
+        if estimator == "Davis-Peebles":
+            return nr / nb * dd / dr - 1.0
+        if estimator == "Hewett":
+            return (nr * nr) / (na * nb) * dd / rr - nr / na * dr / rr
+        if estimator == "Hamilton":
+            return dd * rr / (dr * dr) - 1.0
+        return (nr * nr) / (na * nb) * dd / rr - nr / na * 2.0 * dr / rr + 1.0
+
+
+_USES_DR = ("Davis-Peebles", "Hewett", "Hamilton", "Landy-Szalay")
+_USES_RR = ("Natural", "Hewett", "Hamilton", "Landy-Szalay")
+
+
+def _correlate(pos1, pos2, randoms, s, mu, period, estimator, do_auto, do_cross, vel1=None, vel2=None, los=2):
+    """The xi terms asked for and the dict of raw counts; ``s`` / ``mu`` are checked edges."""
+    _check_estimator(estimator)
+    if not (do_auto or do_cross):
+        raise ValueError("do_auto and do_cross are both False: nothing to compute")
+    if period is None and randoms is None:
+        raise ValueError("period=None (open boundaries) needs randoms")
+    auto1 = do_auto or pos2 is None
+    auto2 = do_auto and pos2 is not None
+    cross = do_cross and pos2 is not None
+    n1, n2 = len(pos1), 0 if pos2 is None else len(pos2)
+    f64 = lambda c: c.astype(np.float64)
+
+    def unordered(pos, vel):
+        if period is not None:
+            return _counts(pos, period, s, mu, vel, los)
+        return _cross(pos, None, None, s, mu, vel1=vel, los=los)
+
+    c = {}
+    if auto1:
+        c["D1D1"] = unordered(pos1, vel1)
+    if cross:
+        c["D1D2"] = _cross(pos1, pos2, period, s, mu, vel1=vel1, vel2=vel2, los=los)
+    if auto2:
+        c["D2D2"] = unordered(pos2, vel2)
+    xi = {}
+    if randoms is None:
+        if auto1:
+            xi[11] = _xi(c["D1D1"], n1, period, s, mu)
+        if auto2:
+            xi[22] = _xi(c["D2D2"], n2, period, s, mu)
+        if cross:
+            shell = (4.0 * np.pi / 3.0) * (s[1:] ** 3 - s[:-1] ** 3)
+            if mu is not None:
+                shell = np.outer(shell, np.diff(mu))
+            with np.errstate(divide="ignore", invalid="ignore"):
+                xi[12] = f64(c["D1D2"]) / (float(n1) * float(n2) * shell / float(period) ** 3) - 1.0
+    else:
+        nr = len(randoms)
+        dr1 = dr2 = rr = None
+        if estimator in _USES_DR:
+            c["D1R"] = _cross(pos1, randoms, period, s, mu, vel1=vel1, los=los)
+            dr1 = f64(c["D1R"])
+            if auto2:
+                c["D2R"] = _cross(pos2, randoms, period, s, mu, vel1=vel2, los=los)
+                dr2 = f64(c["D2R"])
+        if estimator in _USES_RR:
+            c["RR"] = unordered(randoms, None)
+            rr = 2.0 * f64(c["RR"])
+        if auto1:
+            xi[11] = _estimate(estimator, 2.0 * f64(c["D1D1"]), dr1, rr, n1, n1, nr)
+        if cross:
+            xi[12] = _estimate(estimator, f64(c["D1D2"]), dr1, rr, n1, n2, nr)
+        if auto2:
+            xi[22] = _estimate(estimator, 2.0 * f64(c["D2D2"]), dr2, rr, n2, n2, nr)
+    if pos2 is None:
+        out = xi[11]
+    elif do_auto and do_cross:
+        out = (xi[11], xi[12], xi[22])
+    elif do_cross:
+        out = xi[12]
+    else:
+        out = (xi[11], xi[22])
+    return out, c
+
+
 class TPCF:
     """Two Point Correlation Function in redshift space."""
 
@@ -68,6 +190,12 @@ class TPCF:
         nthreads: int = 1,
         los: Optional[int] = None,
         return_counts: bool = False,
+        pos2=None,
+        vel2=None,
+        randoms=None,
+        do_auto: bool = True,
+        do_cross: bool = True,
+        estimator: str = "Landy-Szalay",
     ):
         """xi(s, mu) of a periodic box in redshift space.
 
@@ -77,10 +205,14 @@ class TPCF:
             s_range: s edges, or a tuple (min, max) -> ``linspace(min, max, 40)``.
             mu_range: mu edges, or a tuple (min, max) -> ``sort(1 - geomspace(min, max, 40))``.
             los: line-of-sight axis; None means 2.
-            return_counts: also return the int64 unordered pair counts.
+            return_counts: also return the int64 unordered pair counts (a dict of counts with ``pos2`` or ``randoms``).
+            pos2, vel2: a second sample, shifted and wrapped like the first.
+            randoms: (NR, 3) random positions, not shifted; None: analytic randoms.
+            do_auto, do_cross, estimator: as ``s_mu_tpcf`` (module docstring).
 
         Returns:
-            (s bin centres, mu edges, xi of shape (ns, nmu)) [, counts].
+            (s bin centres, mu edges, xi of shape (ns, nmu)) [, counts]; with ``pos2``, xi is what ``s_mu_tpcf``
+            returns for two samples.
         """
         from ... import device as dev
 
@@ -92,7 +224,8 @@ class TPCF:
             raise ValueError("mu_range is required (redshift-space xi(s, mu))")
         s_range, mu_range = dev.check_tpcf_edges(s_range, mu_range, boxsize)
         out = TPCF.tpcf_s(pos, vel, s_range, mu_range, 2 if los is None else los, boxsize, nthreads,
-                          return_counts=return_counts)
+                          return_counts=return_counts, pos2=pos2, vel2=vel2, randoms=randoms, do_auto=do_auto,
+                          do_cross=do_cross, estimator=estimator)
         centres = (s_range[1:] + s_range[:-1]) / 2.0
         if return_counts:
             return centres, mu_range, out[0], out[1]
@@ -108,30 +241,68 @@ class TPCF:
         boxsize: float = 500.0,
         nthreads: int = 1,
         return_counts: bool = False,
+        pos2=None,
+        vel2=None,
+        randoms=None,
+        do_auto: bool = True,
+        do_cross: bool = True,
+        estimator: str = "Landy-Szalay",
     ):
         """xi(s, mu) in redshift space (Landy-Szalay, analytic randoms): shape (len(chi_range) - 1,
-        len(mu_range) - 1); with ``return_counts`` also the int64 unordered pair counts."""
+        len(mu_range) - 1); with ``return_counts`` also the int64 unordered pair counts.  With ``pos2`` / ``vel2``
+        and / or ``randoms``: the terms of ``s_mu_tpcf`` for the shifted samples, and a dict of counts."""
         from ... import device as dev
 
+        _check_estimator(estimator)
         s, mu = dev.check_tpcf_edges(chi_range, mu_range, boxsize)
         if mu is None:
             raise ValueError("mu_range is required (redshift-space xi(s, mu))")
+        if pos2 is not None or randoms is not None:
+            if pos2 is None and vel2 is not None:
+                raise ValueError("vel2 given without pos2")
+            xi, c = _correlate(pos, pos2, randoms, s, mu, boxsize, estimator, do_auto, do_cross, vel1=vel, vel2=vel2,
+                               los=los)
+            return (xi, c) if return_counts else xi
         dd = _counts(pos, boxsize, s, mu, vel, los)
         xi = _xi(dd, len(pos), boxsize, s, mu)
         return (xi, dd) if return_counts else xi
 
 
-def tpcf_r(pos, rbins, period, estimator: str = "Natural", return_counts: bool = False):
-    """Real-space xi(r) of a periodic box, the subset of halotools' ``tpcf`` the reference calls
-    (``sample1``, ``rbins``, ``period``, ``estimator``; analytic randoms): shape (len(rbins) - 1,); with
-    ``return_counts`` also the int64 unordered pair counts."""
+def tpcf_r(pos, rbins, period=None, estimator: str = "Natural", return_counts: bool = False, sample2=None, randoms=None,
+           do_auto: bool = True, do_cross: bool = True):
+    """Real-space xi(r), halotools' ``tpcf`` (``sample1``, ``rbins``, ``period``, ``estimator``, ``sample2``,
+    ``randoms``, ``do_auto``, ``do_cross``; module docstring): each term of shape (len(rbins) - 1,).  With
+    ``return_counts`` also the int64 unordered pair counts of ``pos``, or, with ``sample2`` or ``randoms``, the dict of
+    raw counts."""
     from ... import device as dev
 
     _check_estimator(estimator)
+    if sample2 is not None or randoms is not None or period is None:
+        return s_mu_tpcf(pos, rbins, None, sample2=sample2, randoms=randoms, period=period, do_auto=do_auto,
+                         do_cross=do_cross, estimator=estimator, return_counts=return_counts)
+    if not (do_auto or do_cross):
+        raise ValueError("do_auto and do_cross are both False: nothing to compute")
     r, _ = dev.check_tpcf_edges(rbins, None, period)
     dd = _counts(pos, period, r, None, None, 2)
     xi = _xi(dd, len(pos), period, r)
     return (xi, dd) if return_counts else xi
+
+
+def s_mu_tpcf(sample1, s_bins, mu_bins, sample2=None, randoms=None, period=None, do_auto: bool = True,
+              do_cross: bool = True, estimator: str = "Natural", los: int = 2, return_counts: bool = False):
+    """xi(s, mu) with halotools' ``s_mu_tpcf`` arguments (module docstring): each term of shape (len(s_bins) - 1,
+    len(mu_bins) - 1), or (len(s_bins) - 1,) with ``mu_bins=None``.  No redshift-space shift: the samples are used as
+    given, with axis ``los`` the line of sight.  With ``return_counts`` also the dict of raw int64 counts."""
+    from ... import device as dev
+
+    _check_estimator(estimator)
+    if not (do_auto or do_cross):
+        raise ValueError("do_auto and do_cross are both False: nothing to compute")
+    if period is None and randoms is None:
+        raise ValueError("period=None (open boundaries) needs randoms")
+    s, mu = dev.check_tpcf_edges(s_bins, mu_bins, period, periodic=period is not None)
+    xi, c = _correlate(sample1, sample2, randoms, s, mu, period, estimator, do_auto, do_cross, los=los)
+    return (xi, c) if return_counts else xi
 
 
 def tpcf_multipole(xi_s_mu, mu_bins, order: int = 0):

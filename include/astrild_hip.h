@@ -912,6 +912,32 @@ int ast_tpcf_pair_counts(void* work_d, size_t work_bytes, size_t n, double boxsi
                          int ns, const double* mu_edges_d, int nmu, int single_cell, unsigned long long* counts_d,
                          void* stream);
 
+/* The same pair counts for two samples, in a periodic cube or with open boundaries: what halotools' tpcf / s_mu_tpcf
+ * count for sample2= and randoms= (particles/hutils/tpcf.py; the reference's halo code correlates the two halves of a
+ * mass-split catalogue that way, stats_subfind.py:155-218).  Two calls on one workspace of
+ * ast_tpcf_cross_workspace_bytes(n1, n2, ns, nmu) bytes (0 for the bin counts ast_tpcf_workspace_bytes refuses):
+ *
+ * ast_tpcf_cross_prepare: ast_tpcf_prepare for each set, with dtypes of its own: the redshift-space shift along los
+ * when velN_d != NULL, and boxsize > 0 the single wrap; boxsize == 0 means open boundaries (shift, no wrap).
+ * bounds_d[12] receives min (x, y, z), max (x, y, z) of set 1, then of set 2 (NaN counts as -inf / +inf; (+inf, -inf)
+ * for an empty set): the caller checks [0, boxsize], or that everything is finite.
+ *
+ * ast_tpcf_cross_counts: auto_pairs == 0: every pair (i of set 1, j of set 2) once; auto_pairs != 0: set 2 is
+ * ignored and the unordered pairs i < j of set 1 are counted (with boxsize > 0 this is ast_tpcf_pair_counts; with
+ * boxsize == 0 its open-boundary twin).  boxsize > 0: minimum image a = min(|dx|, boxsize - |dx|); boxsize == 0:
+ * a = |dx|.  d2, mu, the bins (s_k^2 < d2 <= s_{k+1}^2, mu_l < mu <= mu_{l+1}; d2 = 0 never counts, so coincident
+ * points of the two sets drop out) and counts_d are ast_tpcf_pair_counts'; counts are exact for n1, n2 < 2^31 and zero
+ * when a set is empty (auto: n1 < 2).  Pair finder: one cell grid shared by both sets, each sorted on it: the periodic
+ * grid of ast_tpcf_pair_counts, or for open boundaries a grid over the union bounding box with cells at least the top
+ * s edge wide (1 cell on an axis without extent); single_cell != 0 forces one cell. */
+size_t ast_tpcf_cross_workspace_bytes(size_t n1, size_t n2, int ns, int nmu);
+int ast_tpcf_cross_prepare(const void* pos1_d, int pos1_dtype, const void* vel1_d, int vel1_dtype, size_t n1,
+                           const void* pos2_d, int pos2_dtype, const void* vel2_d, int vel2_dtype, size_t n2, int los,
+                           double boxsize, void* work_d, size_t work_bytes, double* bounds_d, void* stream);
+int ast_tpcf_cross_counts(void* work_d, size_t work_bytes, size_t n1, size_t n2, int auto_pairs, double boxsize,
+                          int los, const double* s_edges_d, int ns, const double* mu_edges_d, int nmu,
+                          int single_cell, unsigned long long* counts_d, void* stream);
+
 /* ------------------------------------------------- radial profiles on 2D maps */
 
 /* Annulus sums and counts of objects on a 2D map: profiles/profile_2d.py (from_map, :10-59, and profiling, :92-153),
