@@ -178,6 +178,16 @@ SIGNATURES = {
     "ast_profile2d_band_rows": (_i, []),
     "ast_profile2d_workspace_bytes": (_sz, [_sz, _sz, _i]),
     "ast_profile2d": (_i, [_vp, _i, _sz, _sz, _sz, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
+    "ast_profile3d_max_bins": (_i, []),
+    "ast_profile3d_layers": (_i, []),
+    "ast_profile3d_chunk": (_i, []),
+    "ast_profile3d_max_cells": (_sz, []),
+    "ast_profile3d_workspace_bytes": (_sz, [_sz, _sz, _sz, _i, _i]),
+    "ast_profile3d_prepare": (_i, [_vp, _i, _vp, _i, _vp, _i, _sz, _i, _vp, _sz, _vp, _vp]),
+    "ast_profile3d_search": (_i, [_vp, _sz, _sz, _i, _d, _d, _d, _d, _d, _d, _d, _d, _sz, _vp, _vp, _vp, _vp, _i, _vp,
+                                  _sz, _vp, _sz, _vp, _i, _i, _vp, _vp, _vp]),
+    "ast_profile3d_members": (_i, [_vp, _sz, _sz, _d, _sz, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp, _sz, _vp, _i, _i, _vp,
+                                   _vp, _vp]),
     "ast_tunnels_workspace_bytes": (_sz, [_sz, _i]),
     "ast_tunnels_max_npix": (_i, []),
     "ast_tunnels_find": (_i, [_vp, _vp, _sz, _i, _i, _vp, _sz, _vp, _vp, _vp]),

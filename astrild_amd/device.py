@@ -1645,6 +1645,199 @@ def annulus_profiles(skymap, x_pix, y_pix, rad_pix, extend, nbins, delta_eta=Non
     return sums, counts
 
 
+# ------------------------------------------------------------------ spherical profiles around centres
+PROFILE3D_OCCUPANCY = 4             # mean particles per cell the search grid aims at
+PROFILE3D_CELL_CAP = 1 << 21        # default cap on the search grid's cells (128^3)
+
+
+def _host_array(a, dtype=None):
+    if isinstance(a, torch.Tensor):
+        a = a.detach().cpu().numpy()
+    return np.ascontiguousarray(a, dtype=dtype)
+
+
+def _icbrt(n):
+    """Largest integer d with d^3 <= n."""
+    d = int(round(float(n) ** (1.0 / 3.0)))
+    while d ** 3 > n:
+        d -= 1
+    while (d + 1) ** 3 <= n:
+        d += 1
+    return d
+
+
+def profile3d_dims(npart, cell_cap=None):
+    """Cells per axis of the search grid of ``sphere_profiles``: a pure function of the particle count and the cell cap
+    (no look at the data, so the host can plan the work list without a read-back): about PROFILE3D_OCCUPANCY particles
+    per cell, at most ``cell_cap`` (default PROFILE3D_CELL_CAP) cells, at least one."""
+    cap = PROFILE3D_CELL_CAP if cell_cap is None else int(cell_cap)
+    if cap < 1:
+        raise ValueError(f"cell_cap must be at least 1, got {cell_cap}")
+    cap = min(cap, 1 << 24)                 # ast_profile3d_max_cells()
+    return max(1, min(_icbrt(max(int(npart), 1) // PROFILE3D_OCCUPANCY), _icbrt(cap)))
+
+
+def check_profile3d_args(pos_shape, centres, radii, edges, boxsize=None, weights_shape=None, vel_shape=None,
+                         centre_vel=None, segments=None, max_bins=256):
+    """The host-side argument checks of ``sphere_profiles``: fp64 ``(centres, radii, edges, centre_vel, segments)``
+    (the last two None when not given) or ValueError."""
+    if len(pos_shape) != 2 or pos_shape[1] != 3:
+        raise ValueError(f"pos must be (Np, 3), got {tuple(pos_shape)}")
+    n = pos_shape[0]
+    if weights_shape is not None and tuple(weights_shape) != (n,):
+        raise ValueError(f"weights must be (Np,) = ({n},), got {tuple(weights_shape)}")
+    if vel_shape is not None and tuple(vel_shape) != (n, 3):
+        raise ValueError(f"vel must be (Np, 3) like pos, got {tuple(vel_shape)}")
+    e = _host_array(edges, np.float64).reshape(-1)
+    if len(e) < 2 or not np.all(np.isfinite(e)) or np.any(np.diff(e) <= 0) or e[0] < 0:
+        raise ValueError("edges must be at least two finite, non-negative, strictly increasing values")
+    if len(e) - 1 > max_bins:
+        raise ValueError(f"{len(e) - 1} bins: at most {max_bins}")
+    c = _host_array(centres, np.float64)
+    if c.ndim != 2 or c.shape[1] != 3:
+        raise ValueError(f"centres must be (Nc, 3), got {c.shape}")
+    nc = c.shape[0]
+    if not np.all(np.isfinite(c)):
+        raise ValueError("centres must be finite")
+    r = _host_array(radii, np.float64)
+    if r.shape != (nc,):
+        raise ValueError(f"radii must be (Nc,) = ({nc},), got {r.shape}")
+    if not (np.all(np.isfinite(r)) and np.all(r > 0)):
+        raise ValueError("radii must be positive and finite")
+    cv = None
+    if centre_vel is not None:
+        if vel_shape is None:
+            raise ValueError("centre_vel given without vel")
+        cv = _host_array(centre_vel, np.float64)
+        if cv.shape != (nc, 3) or not np.all(np.isfinite(cv)):
+            raise ValueError(f"centre_vel must be finite and (Nc, 3) = ({nc}, 3), got {cv.shape}")
+    if boxsize is not None:
+        box = float(boxsize)
+        if not (np.isfinite(box) and box > 0):
+            raise ValueError(f"boxsize must be positive and finite, got {boxsize}")
+        if nc and not np.max(e[-1] * r) < box / 2.0:
+            raise ValueError(f"the largest reach edges[-1] * radius ({np.max(e[-1] * r)}) must be below boxsize / 2 "
+                             f"({box / 2.0})")
+        if nc and not (np.all(c >= 0.0) and np.all(c <= box)):
+            raise ValueError(f"centres must lie in [0, {box}]")
+    seg = None
+    if segments is not None:
+        seg = _host_array(segments)
+        if seg.shape != (nc, 2) or not np.issubdtype(seg.dtype, np.integer):
+            raise ValueError(f"segments must be integer (offset, count) pairs, (Nc, 2) = ({nc}, 2), got {seg.shape} "
+                             f"{seg.dtype}")
+        seg = seg.astype(np.int64)
+        if nc and not (np.all(seg >= 0) and np.all(seg[:, 0] + seg[:, 1] <= n)):
+            raise ValueError(f"segments must lie within [0, Np] = [0, {n}]")
+    return c, r, e, cv, seg
+
+
+def _profile3d_axis_range(c, reach, lo, inv, dims, periodic):
+    """(first cell, number of cells) that [c - reach, c + reach] touches on one axis: p3_axis_range of profile3d.hip."""
+    big = float(1 << 30)
+    a = np.clip(np.floor((c - reach - lo) * inv), -big, big).astype(np.int64)
+    b = np.clip(np.floor((c + reach - lo) * inv), -big, big).astype(np.int64)
+    if periodic:
+        full = b - a + 1 >= dims
+        return np.where(full, 0, np.mod(a, dims)), np.where(full, dims, b - a + 1)
+    a, b = np.maximum(a, 0), np.minimum(b, dims - 1)
+    ok = b >= a
+    return np.where(ok, a, 0), np.where(ok, b - a + 1, 0)
+
+
+def sphere_profiles(pos, centres, radii, edges, boxsize=None, weights=None, vel=None, centre_vel=None, segments=None,
+                    cell_cap=None):
+    """Radial histograms of particles around centres (ast_profile3d_*; the reference's profiles/profile_3d.py): device
+    tensors ``(counts, moments)``, (Nc, nbins) int64 and (Nc, nbins, M) float64 with M = 1 (the sum of w) or, with
+    ``vel``, M = 4 (the sums of w, w v_r, w v_r^2, w |u|^2; u = v - centre_vel, v_r = u.s / d, 0 at d = 0).  ``edges``
+    are in units of each centre's radius.  Per particle s = p - c, with ``boxsize`` wrapped once per axis (s > L/2 ->
+    s - L, else s < -L/2 -> s + L; ``boxsize=None``: open, plain separations), d^2 = (sx^2 + sy^2) + sz^2 in fp64 and
+    x = sqrt(d^2) / R goes to bin k when e_k <= x < e_{k+1}, the last bin also taking x == e_last: np.histogram's rule.
+    A particle at distance 0 counts when e_0 == 0 - unlike the pair counts of the TPCF, which never count d = 0.
+    ``segments=None``: every particle in reach is found through a cell grid of ``profile3d_dims(Np, cell_cap)``^3 cells.
+    ``segments`` (Nc, 2) integer (offset, count): centre i bins only particles offset_i .. offset_i + count_i - 1 (the
+    reference's cum_N_particles / N_particles).  ``pos`` / ``weights`` / ``vel``: numpy arrays or device tensors,
+    float32 or float64; centres, radii and centre_vel: host arrays or tensors (the work list is built on the host).
+    ValueError before any GPU work for shapes, dtypes, edges, radii that are not positive and finite, a periodic reach
+    max(edges[-1] * radii) >= boxsize / 2, periodic centres outside [0, boxsize], segments outside [0, Np]; and from the
+    device bounds for periodic positions outside [0, boxsize] or open positions that are not finite.  Nc = 0 or Np = 0
+    returns zeros without a launch.  ASTRILD_PROFILE3D_CELLS=0 forces one cell, ASTRILD_PROFILE3D_LAYERS=0 one work
+    item per centre (both for the tests)."""
+    lib = _lib.lib()
+    shape = lambda t: None if t is None else tuple(np.shape(t))
+    c, r, e, cv, seg = check_profile3d_args(shape(pos), centres, radii, edges, boxsize, shape(weights), shape(vel),
+                                            centre_vel, segments, max_bins=lib.ast_profile3d_max_bins())
+    periodic = boxsize is not None
+    box = float(boxsize) if periodic else 0.0
+    n, nc, nbins, nmom = int(shape(pos)[0]), len(r), len(e) - 1, 4 if vel is not None else 1
+    real = lambda t: None if t is None else (lambda d: d if d.dtype in _REAL else d.to(torch.float64))(as_device(t))
+    p, w, v = real(pos), real(weights), real(vel)
+    if nc == 0 or n == 0:
+        return (torch.zeros((nc, nbins), dtype=torch.int64, device=p.device),
+                torch.zeros((nc, nbins, nmom), dtype=torch.float64, device=p.device))
+    search = seg is None
+    single = os.environ.get("ASTRILD_PROFILE3D_CELLS", "1") == "0"
+    dims = (1 if single else profile3d_dims(n, cell_cap)) if search else 0
+    ncells = dims ** 3
+    st = stream()
+    code = lambda t: real_code(t) if t is not None else F64
+    bounds = torch.empty(6, dtype=torch.float64, device=p.device)
+
+    def prepare(work, ws_bytes, bounds_only=False):
+        check(lib.ast_profile3d_prepare(ptr(p), code(p), ptr(w), code(w), ptr(v), code(v), n, int(bounds_only),
+                                        ptr(work), ws_bytes, ptr(bounds), st), "ast_profile3d_prepare")
+        b = to_numpy(bounds)
+        if periodic and not (np.all(b[:3] >= 0.0) and np.all(b[3:] <= box)):
+            raise ValueError(f"positions must lie in [0, {box}]: min {b[:3].tolist()}, max {b[3:].tolist()}")
+        if not periodic and not np.all(np.isfinite(b)):
+            raise ValueError(f"positions must be finite: min {b[:3].tolist()}, max {b[3:].tolist()}")
+        return b
+
+    if search and not periodic:
+        # open boundaries: the grid spans the bounding box and the work list (hence the workspace's size) follows from
+        # it, so a bounds-only pass over the positions comes first; it writes no records
+        b = prepare(torch.empty(256, dtype=torch.uint8, device=p.device), 256, bounds_only=True)
+        lo, ext = b[:3].copy(), b[3:] - b[:3]
+        inv = np.where(ext > 0.0, dims / np.where(ext > 0.0, ext, 1.0), 0.0) if dims > 1 else np.zeros(3)
+        pad = 1e-12 * float(np.max(np.abs(b)))
+    elif search:
+        lo = np.zeros(3)
+        inv = np.full(3, dims / box if dims > 1 else 0.0)
+        pad = 1e-12 * box
+    if search:
+        reach = (e[-1] * r) * (1.0 + 1e-9) + pad
+        z0, nz = _profile3d_axis_range(c[:, 2], reach, lo[2], inv[2], dims, periodic)
+        per = lib.ast_profile3d_layers() if os.environ.get("ASTRILD_PROFILE3D_LAYERS", "1") != "0" else 0
+        per_centre = np.maximum(1, -(-nz // per)) if per else np.ones(nc, dtype=np.int64)
+        zrange = as_device(np.ascontiguousarray(np.stack([z0, nz], axis=1), dtype=np.int32))
+    else:
+        per = lib.ast_profile3d_chunk()
+        per_centre = np.maximum(1, -(-seg[:, 1] // per))
+        seg_d = as_device(seg)
+    item_start = np.zeros(nc + 1, dtype=np.int64)
+    np.cumsum(per_centre, out=item_start[1:])
+    part_start = np.zeros(nc + 1, dtype=np.int64)
+    np.cumsum(np.where(per_centre > 1, per_centre, 0), out=part_start[1:])
+    n_items, n_part = int(item_start[-1]), int(part_start[-1])
+    ws_bytes = lib.ast_profile3d_workspace_bytes(n, ncells, n_part, nbins, nmom)
+    work = torch.empty(ws_bytes, dtype=torch.uint8, device=p.device)
+    prepare(work, ws_bytes)
+    c_d, r_d, e_d, cv_d = as_device(c), as_device(r), as_device(e), as_device(cv) if cv is not None else None
+    starts, parts = as_device(item_start), as_device(part_start)
+    counts = torch.empty((nc, nbins), dtype=torch.int64, device=p.device)
+    moments = torch.empty((nc, nbins, nmom), dtype=torch.float64, device=p.device)
+    if search:
+        check(lib.ast_profile3d_search(ptr(work), ws_bytes, n, dims, lo[0], lo[1], lo[2], inv[0], inv[1], inv[2], box,
+                                       pad, nc, ptr(c_d), ptr(r_d), ptr(cv_d), ptr(zrange), per, ptr(starts), n_items,
+                                       ptr(parts), n_part, ptr(e_d), nbins, nmom, ptr(counts), ptr(moments), st),
+              "ast_profile3d_search")
+    else:
+        check(lib.ast_profile3d_members(ptr(work), ws_bytes, n, box, nc, ptr(c_d), ptr(r_d), ptr(cv_d), ptr(seg_d), per,
+                                        ptr(starts), n_items, ptr(parts), n_part, ptr(e_d), nbins, nmom, ptr(counts),
+                                        ptr(moments), st), "ast_profile3d_members")
+    return counts, moments
+
+
 # ------------------------------------------------------------------ tunnels void finder
 def check_tunnels_tracers(x_pix, y_pix, npix):
     """The argument checks of ``tunnels_voids``, before any GPU work: ``(x, y, npix, on_device)`` with x, y 1D integer

@@ -961,6 +961,65 @@ int ast_profile2d(const void* map_d, int dtype, size_t ny, size_t nx, size_t n_o
                   const long long* item_start_d, size_t n_work, void* work_d, size_t work_bytes, double* sums_d,
                   long long* counts_d, void* stream);
 
+/* ------------------------------------------------- spherical profiles of particles around centres */
+
+/* Per-centre radial histograms of particles: profiles/profile_3d.py (Profiles3D.get_one_profile / from_particle_data),
+ * for haloes (edges in units of r200c) and voids (in units of the void radius).  For centre o with radius R_o and every
+ * particle p it looks at: s = p - c_o, with boxsize > 0 wrapped once per axis (s > L/2 -> s - L, else s < -L/2 -> s + L;
+ * boxsize == 0: plain separations), d2 = (sx^2 + sy^2) + sz^2, x = sqrt(d2) / R_o, all fp64.  The particle counts in bin
+ * k when e_k <= x < e_{k+1}, and the last bin also takes x == e_nbins (np.histogram's rule; unlike the pair counts above a
+ * particle at distance 0 counts when e_0 == 0).  counts_d (nc, nbins) int64 receives the counts and moments_d
+ * (nc, nbins, nmom) fp64 the sums of w (nmom == 1) or of w, w v_r, w v_r^2, w |u|^2 (nmom == 4), u = v - centre
+ * velocity (centre_vel_d == NULL: 0), v_r = ((ux sx + uy sy) + uz sz) / sqrt(d2), 0 at d2 == 0.  The counts are exact;
+ * the sums are formed with LDS atomics inside a work item (their order is not fixed) and in item order across items.
+ *
+ * ast_profile3d_prepare: every particle becomes one 64-byte fp64 record (r, w, v); weights_d == NULL: w = 1, vel_d ==
+ * NULL: v = 0; each array has its own dtype (AST_F32 / AST_F64).  bounds_d[6] receives min (x, y, z), max (x, y, z) of
+ * the positions (NaN counts as -inf / +inf; (+inf, -inf) when np == 0): the caller checks [0, boxsize], or that
+ * everything is finite, before it calls one of the two below.  bounds_only != 0: no records are written and the
+ * workspace need only hold 256 bytes (a caller that must know the bounds before it can size the full workspace):
+ *
+ * ast_profile3d_search: the records are sorted into a grid of dims^3 cells (x fastest), cell of a coordinate =
+ * floor((x - lo) * inv) clamped to [0, dims - 1] per axis (periodic: lo = 0, inv = dims / boxsize; open: the bounding
+ * box, inv = 0 on an axis without extent).  Centre o visits the cells that [c - reach, c + reach] touches on each axis,
+ * reach = e_nbins R_o (1 + 1e-9) + pad (pad: the caller's allowance for the rounding of large coordinates); periodic, a
+ * range of >= dims cells visits each cell of the axis once.  zrange_d[2 o], [2 o + 1] = first z cell and number of z
+ * layers of centre o, computed by the caller with that same expression.  Work items are runs of `layers` z layers
+ * (ast_profile3d_layers(); 0: one item per centre).
+ *
+ * ast_profile3d_members: centre o looks only at records segments_d[2 o] .. + segments_d[2 o + 1] - 1 of the unsorted
+ * array (the reference's cum_N_particles / N_particles); work items are chunks of `chunk` members
+ * (ast_profile3d_chunk()).
+ *
+ * Both: centre o owns items item_start_d[o] .. item_start_d[o + 1] - 1, at least one each (item_start_d[0] = 0,
+ * item_start_d[nc] = n_items).  A centre with one item is written straight into counts_d / moments_d; the items of a
+ * centre with several go to partial rows part_start_d[o] + k (part_start_d[nc] = n_part, the number of such items) and
+ * are summed in item order.  Workspace: ast_profile3d_workspace_bytes(np, ncells, n_part, nbins, nmom) =
+ * 64 np (records) + [ncells > 0: 64 np (sorted) + 4 np + 12 ncells + 4 ceil(ncells / 2048) (grid)] +
+ * 8 n_part nbins (1 + nmom), each array
+ * rounded up to 256 bytes (ncells = dims^3 for the search, 0 for members); it does not grow with the number of
+ * single-item centres.  0: nbins outside 1..ast_profile3d_max_bins(), nmom not 1 or 4, ncells >
+ * ast_profile3d_max_cells(), or np >= 2^31. */
+int ast_profile3d_max_bins(void);
+int ast_profile3d_layers(void);
+int ast_profile3d_chunk(void);
+size_t ast_profile3d_max_cells(void);
+size_t ast_profile3d_workspace_bytes(size_t np, size_t ncells, size_t n_part, int nbins, int nmom);
+int ast_profile3d_prepare(const void* pos_d, int pos_dtype, const void* weights_d, int weights_dtype, const void* vel_d,
+                          int vel_dtype, size_t np, int bounds_only, void* work_d, size_t work_bytes, double* bounds_d,
+                          void* stream);
+int ast_profile3d_search(void* work_d, size_t work_bytes, size_t np, int dims, double lo_x, double lo_y, double lo_z,
+                         double inv_x, double inv_y, double inv_z, double boxsize, double pad, size_t nc,
+                         const double* centres_d, const double* radii_d, const double* centre_vel_d,
+                         const int* zrange_d, int layers, const long long* item_start_d, size_t n_items,
+                         const long long* part_start_d, size_t n_part, const double* edges_d, int nbins, int nmom,
+                         long long* counts_d, double* moments_d, void* stream);
+int ast_profile3d_members(void* work_d, size_t work_bytes, size_t np, double boxsize, size_t nc,
+                          const double* centres_d, const double* radii_d, const double* centre_vel_d,
+                          const long long* segments_d, int chunk, const long long* item_start_d, size_t n_items,
+                          const long long* part_start_d, size_t n_part, const double* edges_d, int nbins, int nmom,
+                          long long* counts_d, double* moments_d, void* stream);
+
 /* ------------------------------------------------- tunnels void finder */
 
 /* The tunnels void finder of rays/voids/tunnel.py (TunnelsFinder.find_voids, :158-248; Cautun et al.,
