@@ -28,13 +28,15 @@ def angles_and_velocities(pos, vel_ang, theta1=None, theta2=None):
     return pos / nr[:, None], t
 
 
-def pair_sums(pos, u, t, binnr, binwidth, rows=None):
-    """(nom, denom, counts) over all pairs i < j; `rows`: only these i (for timing a sample)."""
+def pair_sums(pos, u, t, binnr, binwidth, rows=None, with_abs=False):
+    """(nom, denom, counts) over all pairs i < j; `rows`: only these i (for timing a sample).  `with_abs`: also the
+    per-bin sum of |term| of nom, for the error bound of a reordered sum (denom's terms are positive: it is its own)."""
     pos = np.asarray(pos, dtype=np.float64)
     n = len(pos)
     nom = np.zeros(binnr)
     den = np.zeros(binnr)
     cnt = np.zeros(binnr, dtype=np.int64)
+    sum_abs = np.zeros(binnr)
     for i in (range(n - 1) if rows is None else rows):
         d = pos[i] - pos[i + 1:]
         nrm = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
@@ -50,10 +52,13 @@ def pair_sums(pos, u, t, binnr, binwidth, rows=None):
             dj = (p[:, 0] * uj[:, 0] + p[:, 1] * uj[:, 1]) + p[:, 2] * uj[:, 2]
             q = 0.5 * ((2.0 * p - ui[None, :] * di[:, None]) - uj * dj[:, None])
             tij = t[i] - t[i + 1:][ok]
-            nom += np.bincount(b, weights=(tij[:, 0] * q[:, 0] + tij[:, 1] * q[:, 1]) + tij[:, 2] * q[:, 2],
-                               minlength=binnr)
+            term = (tij[:, 0] * q[:, 0] + tij[:, 1] * q[:, 1]) + tij[:, 2] * q[:, 2]
+            nom += np.bincount(b, weights=term, minlength=binnr)
+            sum_abs += np.bincount(b, weights=np.abs(term), minlength=binnr)
             den += np.bincount(b, weights=(q[:, 0] * q[:, 0] + q[:, 1] * q[:, 1]) + q[:, 2] * q[:, 2], minlength=binnr)
         cnt += np.bincount(b, minlength=binnr)
+    if with_abs:
+        return nom, den, cnt, sum_abs
     return nom, den, cnt
 
 
