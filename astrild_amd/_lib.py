@@ -24,6 +24,8 @@ PAINT_STAGE_GROUP_PART, PAINT_STAGE_RESET, PAINT_STAGE_LATE = 3, 4, 5
 PVPDF_KIND = {"z_sign": 0, "radial": 1}     # AST_PVPDF_*
 PVPDF_MAX_BINS = 1 << 22                    # ast_pairwise_pdf_max_bins(), known here so that arguments are checked
 PVPDF_MAX_MOMENT_ROWS = 480                 # without a library call (AST_PVPDF_MAX_MOMENT_ROWS)
+PAIRVEL_KIND = {"radial": 0, "los": 1}      # AST_PAIRVEL_*
+PAIRVEL_MAX_BINS = 511                      # ast_pairvel_max_bins() (AST_PAIRVEL_MAX_BINS), known here likewise
 
 
 class AstrildHipError(RuntimeError):
@@ -174,6 +176,10 @@ SIGNATURES = {
     "ast_tpcf_cross_workspace_bytes": (_sz, [_sz, _sz, _i, _i]),
     "ast_tpcf_cross_prepare": (_i, [_vp, _i, _vp, _i, _sz, _vp, _i, _vp, _i, _sz, _i, _d, _vp, _sz, _vp, _vp]),
     "ast_tpcf_cross_counts": (_i, [_vp, _sz, _sz, _sz, _i, _d, _i, _vp, _i, _vp, _i, _i, _vp, _vp]),
+    "ast_pairvel_workspace_bytes": (_sz, [_sz, _sz, _i]),
+    "ast_pairvel_max_bins": (_i, []),
+    "ast_pairvel_prepare": (_i, [_vp, _i, _vp, _i, _sz, _vp, _i, _vp, _i, _sz, _vp, _sz, _vp, _vp]),
+    "ast_pairvel_moments": (_i, [_vp, _sz, _sz, _sz, _i, _d, _i, _i, _d, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "ast_profile2d_max_bins": (_i, []),
     "ast_profile2d_band_rows": (_i, []),
     "ast_profile2d_workspace_bytes": (_sz, [_sz, _sz, _i]),

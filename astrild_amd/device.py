@@ -1602,6 +1602,127 @@ def tpcf_cross_counts(pos1, pos2, s_edges, mu_edges=None, boxsize=None, vel1=Non
     return counts
 
 
+# ------------------------------------------------------------------ pairwise-velocity moments in a box
+def check_pair_velocity_args(pos1_shape, vel1_shape, edges, pos2_shape=None, vel2_shape=None, boxsize=None,
+                             kind="radial", pi_max=None, los=2):
+    """The argument checks of ``pair_velocity_moments`` on the host, without a library call:
+    ``(edges, box, pi_max, n1, n2)`` - fp64 edges, ``box`` 0.0 for open boundaries, ``pi_max`` 0.0 for "radial",
+    ``n2`` 0 without a second sample - or ValueError.  Edges finite, >= 0, strictly increasing, at most
+    ``_lib.PAIRVEL_MAX_BINS`` bins; with a ``boxsize`` (positive, finite) the top edge, and for "los" also ``pi_max``,
+    below boxsize / 3 (as check_tpcf_edges); "los" needs a positive, finite ``pi_max``; ``los`` 0, 1 or 2; positions
+    (N, 3) with velocities shaped like them; a second sample has both positions and velocities or neither."""
+    if kind not in _lib.PAIRVEL_KIND:
+        raise ValueError(f"kind must be one of {sorted(_lib.PAIRVEL_KIND)}, got {kind!r}")
+    if isinstance(los, bool) or los not in (0, 1, 2):
+        raise ValueError(f"los must be 0, 1 or 2, got {los!r}")
+    periodic = boxsize is not None
+    box = 0.0
+    if periodic:
+        box = float(boxsize)
+        if not (np.isfinite(box) and box > 0):
+            raise ValueError(f"boxsize must be positive and finite, got {box}")
+    e = np.asarray(edges, dtype=np.float64).reshape(-1)
+    if len(e) < 2 or not np.all(np.isfinite(e)) or np.any(np.diff(e) <= 0) or e[0] < 0:
+        raise ValueError("bin edges must be at least two finite, non-negative, strictly increasing values")
+    if len(e) - 1 > _lib.PAIRVEL_MAX_BINS:
+        raise ValueError(f"{len(e) - 1} bins: at most {_lib.PAIRVEL_MAX_BINS}")
+    if periodic and not e[-1] < box / 3.0:
+        raise ValueError(f"the largest bin edge ({e[-1]}) must be below boxsize / 3 ({box / 3.0})")
+    pmax = 0.0
+    if kind == "los":
+        try:
+            pmax = float("nan") if pi_max is None or isinstance(pi_max, (str, bytes)) else float(pi_max)
+        except (TypeError, ValueError):
+            pmax = float("nan")
+        if not (np.isfinite(pmax) and pmax > 0):
+            raise ValueError(f"pi_max must be a positive, finite real number, got {pi_max!r}")
+        if periodic and not pmax < box / 3.0:
+            raise ValueError(f"pi_max ({pmax}) must be below boxsize / 3 ({box / 3.0})")
+    if pos2_shape is None and vel2_shape is not None:
+        raise ValueError("vel2 given without pos2")
+    if pos2_shape is not None and vel2_shape is None:
+        raise ValueError("pos2 given without vel2")
+    ns = []
+    for k, (ps, vs) in enumerate(((pos1_shape, vel1_shape), (pos2_shape, vel2_shape))):
+        if ps is None:
+            ns.append(0)
+            continue
+        if vs is None:
+            raise ValueError(f"sample {k + 1} needs velocities")
+        ps, vs = tuple(ps), tuple(vs)
+        if len(ps) != 2 or ps[1] != 3 or vs != ps:
+            raise ValueError(f"positions and velocities of sample {k + 1} must both be (N, 3), got {ps} and {vs}")
+        if ps[0] >= 1 << 31:
+            raise ValueError(f"sample {k + 1}: fewer than 2^31 objects")
+        ns.append(ps[0])
+    return e, box, pmax, ns[0], ns[1]
+
+
+def pair_velocity_moments(pos1, vel1, edges, pos2=None, vel2=None, boxsize=None, kind="radial", pi_max=None, los=2):
+    """Count, sum v and sum v^2 per separation bin of the pairwise velocity (ast_pairvel_prepare /
+    ast_pairvel_moments): device tensors ``(count, s1, s2)``, (nb,) int64 / float64 / float64, over every pair (i of
+    sample 1, j of sample 2); ``pos2=None``: the unordered pairs i < j of sample 1.  ``boxsize`` given: a periodic
+    cube, each separation component s = x_j - x_i moved by -+ boxsize when beyond +- boxsize / 2; ``boxsize=None``: open
+    boundaries, plain separations.  With dv = v_j - v_i, all in fp64:
+    "radial": d^2 = (s_x^2 + s_y^2) + s_z^2 in bin k when edges_k^2 < d^2 <= edges_{k+1}^2 (a pair at distance 0 is in
+    no bin), v = dv . s / d;  "los": rp^2 = s_a^2 + s_b^2 over the two axes other than ``los`` in bin k when
+    edges_k^2 < rp^2 <= edges_{k+1}^2 and |s_los| <= pi_max, v = dv_los sign(s_los).  The counts of "radial" are those
+    of tpcf_cross_counts on the same edges.  Positions and velocities: (N, 3), numpy arrays or device tensors, float32
+    or float64 in any combination (widened to float64 on load).  ValueError before any library call for bad arguments
+    (check_pair_velocity_args), and from the device bounds before any pair work: periodic, coordinates outside
+    [0, boxsize]; open, any non-finite coordinate.  ASTRILD_PAIRVEL_CELLS=0 forces one cell (all pairs)."""
+    e, box, pmax, n1, n2 = check_pair_velocity_args(
+        np.shape(pos1), np.shape(vel1), edges, None if pos2 is None else np.shape(pos2),
+        None if vel2 is None else np.shape(vel2), boxsize, kind, pi_max, los)
+    periodic = boxsize is not None
+    auto = pos2 is None
+    lib = _lib.lib()
+    sets = []
+    for a in (pos1, vel1) + (() if auto else (pos2, vel2)):
+        t = as_device(a)
+        sets.append(t if t.dtype in _REAL else t.to(torch.float64))
+    p1, v1 = sets[0], sets[1]
+    p2, v2 = (None, None) if auto else (sets[2], sets[3])
+    nb = len(e) - 1
+    single = os.environ.get("ASTRILD_PAIRVEL_CELLS", "1") == "0"
+    ws_bytes = lib.ast_pairvel_workspace_bytes(n1, n2, nb)
+    work = torch.empty(ws_bytes, dtype=torch.uint8, device=p1.device)
+    bounds = torch.empty(12, dtype=torch.float64, device=p1.device)
+    st = stream()
+    code = lambda t: real_code(t) if t is not None else F64
+    check(lib.ast_pairvel_prepare(ptr(p1), code(p1), ptr(v1), code(v1), n1, ptr(p2), code(p2), ptr(v2), code(v2), n2,
+                                  ptr(work), ws_bytes, ptr(bounds), st), "ast_pairvel_prepare")
+    b = to_numpy(bounds).reshape(2, 6)
+    for k, n in enumerate((n1, n2)):
+        if not n:
+            continue
+        if periodic and not (np.all(b[k, :3] >= 0.0) and np.all(b[k, 3:] <= box)):
+            raise ValueError(f"positions of sample {k + 1} must lie in [0, {box}]: "
+                             f"min {b[k, :3].tolist()}, max {b[k, 3:].tolist()}")
+        if not periodic and not np.all(np.isfinite(b[k])):
+            raise ValueError(f"positions of sample {k + 1} must be finite: "
+                             f"min {b[k, :3].tolist()}, max {b[k, 3:].tolist()}")
+    e_d = as_device(e)
+    count = torch.empty(nb, dtype=torch.int64, device=p1.device)
+    s1 = torch.empty(nb, dtype=torch.float64, device=p1.device)
+    s2 = torch.empty(nb, dtype=torch.float64, device=p1.device)
+    check(lib.ast_pairvel_moments(ptr(work), ws_bytes, n1, n2, int(auto), box, _lib.PAIRVEL_KIND[kind], int(los), pmax,
+                                  ptr(e_d), nb, int(single), ptr(count), ptr(s1), ptr(s2), st), "ast_pairvel_moments")
+    return count, s1, s2
+
+
+def finish_pair_velocity(count, s1, s2):
+    """``(mean, sigma)`` per bin from the moments, host fp64: mean = s1 / count,
+    sigma = sqrt(max(s2 / count - mean^2, 0)); NaN in empty bins.  Device tensors or arrays."""
+    c, a, b = (to_numpy(x) if isinstance(x, torch.Tensor) else np.asarray(x) for x in (count, s1, s2))
+    c, a, b = c.astype(np.float64), a.astype(np.float64), b.astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean = a / c
+        var = b / c - mean * mean
+        sigma = np.sqrt(np.where(var > 0.0, var, np.where(np.isnan(var), np.nan, 0.0)))
+    return mean, sigma
+
+
 def annulus_profiles(skymap, x_pix, y_pix, rad_pix, extend, nbins, delta_eta=None):
     """Per-annulus sums and pixel counts of objects on a 2D map (profiles/profile_2d.py: from_map / profiling): device
     tensors ``(sums, counts)``, (N, nbins) float64 and int64, the true sums and counts (not the reference's count

@@ -938,6 +938,50 @@ int ast_tpcf_cross_counts(void* work_d, size_t work_bytes, size_t n1, size_t n2,
                           int los, const double* s_edges_d, int ns, const double* mu_edges_d, int nmu,
                           int single_cell, unsigned long long* counts_d, void* stream);
 
+/* ------------------------------------------------- pairwise-velocity moments of one or two samples in a box */
+
+/* Count, sum v and sum v^2 per separation bin of the pairwise velocity of one or two samples, in a periodic cube or
+ * with open boundaries: what halotools' mean_radial_velocity_vs_r / radial_pvd_vs_r / mean_los_velocity_vs_rp /
+ * los_pvd_vs_rp accumulate (the reference's commented-out SubFind.mean_pairwise_velocity, stats_subfind.py:155-218,
+ * asks the first of them for the two halves of a mass-split catalogue).  Two calls on one workspace of
+ * ast_pairvel_workspace_bytes(n1, n2, nb) bytes (0 for nb < 1 or nb > ast_pairvel_max_bins() = AST_PAIRVEL_MAX_BINS):
+ *
+ * ast_pairvel_prepare (stats_subfind.py:155-218): positions and velocities of each set, (n, 3) each and each AST_F32
+ * or AST_F64, are widened exactly to fp64 (no redshift-space shift, no wrap).  bounds_d[12] receives min (x, y, z),
+ * max (x, y, z) of set 1, then of set 2 (NaN counts as -inf / +inf; (+inf, -inf) for an empty set): the caller checks
+ * [0, boxsize], or that everything is finite.  n2 == 0 with NULL pointers for the auto term.
+ *
+ * ast_pairvel_moments (stats_subfind.py:155-218): auto_pairs == 0: every pair (i of set 1, j of set 2) once;
+ * auto_pairs != 0: set 2 is ignored and the unordered pairs i < j of set 1 are taken.  In fp64, op by op:
+ * s_a = x_j[a] - x_i[a], with boxsize > 0 moved by -+ boxsize when beyond +- boxsize / 2 (boxsize == 0: open boundaries,
+ * plain separations), dv = v_j - v_i, and
+ *   AST_PAIRVEL_RADIAL: d2 = (s_x^2 + s_y^2) + s_z^2; bin k when edges[k]^2 < d2 <= edges[k + 1]^2 (a pair at
+ *                       distance 0 is in no bin); v = ((dv_x s_x + dv_y s_y) + dv_z s_z) / sqrt(d2).
+ *   AST_PAIRVEL_LOS:    rp2 = s_a^2 + s_b^2 over the two axes other than los, in axis order; bin k when
+ *                       edges[k]^2 < rp2 <= edges[k + 1]^2 and |s_los| <= pi_max; v = dv_los sign(s_los), sign in
+ *                       {-1, 0, +1}.
+ * |s_a| is bit for bit ast_tpcf_cross_counts' minimum image, so count_d of AST_PAIRVEL_RADIAL equals its counts on
+ * the same edges.  count_d[nb] (exact, the same from call to call), s1_d[nb] = sum v, s2_d[nb] = sum v^2 (fp64 sums
+ * in no fixed order within a workgroup: LDS atomics per wave, then fixed-order sums of the waves and workgroups - no
+ * global float atomics).  All outputs are written, not accumulated; zero when a set is empty (auto: n1 < 2).  Pair
+ * finder: the shared cell grid of ast_tpcf_cross_counts with the reach edges[nb] (radial) or
+ * sqrt(edges[nb]^2 + pi_max^2) (los); single_cell != 0 forces one cell.  n1, n2 < 2^31. */
+#define AST_PAIRVEL_RADIAL 0
+#define AST_PAIRVEL_LOS 1
+#define AST_PAIRVEL_MAX_BINS 511
+/* stats_subfind.py:155-218 */
+size_t ast_pairvel_workspace_bytes(size_t n1, size_t n2, int nb);
+/* stats_subfind.py:155-218: the largest nb */
+int ast_pairvel_max_bins(void);
+/* stats_subfind.py:155-218 */
+int ast_pairvel_prepare(const void* pos1_d, int pos1_dtype, const void* vel1_d, int vel1_dtype, size_t n1,
+                        const void* pos2_d, int pos2_dtype, const void* vel2_d, int vel2_dtype, size_t n2,
+                        void* work_d, size_t work_bytes, double* bounds_d, void* stream);
+/* stats_subfind.py:155-218 */
+int ast_pairvel_moments(void* work_d, size_t work_bytes, size_t n1, size_t n2, int auto_pairs, double boxsize, int kind,
+                        int los, double pi_max, const double* edges_d, int nb, int single_cell,
+                        unsigned long long* count_d, double* s1_d, double* s2_d, void* stream);
+
 /* ------------------------------------------------- radial profiles on 2D maps */
 
 /* Annulus sums and counts of objects on a 2D map: profiles/profile_2d.py (from_map, :10-59, and profiling, :92-153),
