@@ -21,6 +21,16 @@ inline unsigned stream_grid(size_t work_items, unsigned block) {
     return (unsigned)(need > 2048 ? 2048 : need);
 }
 
+// f(TP(), TV()) with TP, TV = float or double: the launch of a kernel templated on two element types, e.g.
+// dispatch_f32_f64(p32, v32, [&](auto tp, auto tv) { kernel<decltype(tp), decltype(tv)><<<...>>>(...); }).
+template <typename F>
+inline void dispatch_f32_f64(bool first_f32, bool second_f32, F&& f) {
+    if (first_f32 && second_f32) f(float(), float());
+    else if (first_f32) f(float(), double());
+    else if (second_f32) f(double(), float());
+    else f(double(), double());
+}
+
 // Optional per-launch HIP-event timing (ast_profile_enable): a scope records an
 // event pair on the launch stream; ast_profile_report aggregates by name.
 struct ProfScope {

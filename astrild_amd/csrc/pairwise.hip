@@ -15,37 +15,18 @@ constexpr int PV_MAX_BINS = 480;            // 4 wave histograms x 24 B x bins +
 
 struct PvObj { double r[3], u[3], t[3]; };
 
-using PvParams = GridBoxParams;
-
-inline size_t cells_cap(size_t n) { return grid_box_cells_cap(n); }
-
-struct PvLayout {
-    size_t params, cnt, cell_start, tile_start, cursor, cell_of, obj, sorted, part, total;
-    PvLayout(size_t n, int binnr) {
-        const size_t cap = cells_cap(n);
-        size_t o = 0;
-        params = o;     o += align256(sizeof(PvParams));
-        cnt = o;        o += align256(cap * 4);
-        cell_start = o; o += align256((cap + 1) * 4);
-        tile_start = o; o += align256((cap + 1) * 4);
-        cursor = o;     o += align256(cap * 4);
-        cell_of = o;    o += align256(n * 4);
-        obj = o;        o += align256(n * sizeof(PvObj));
-        sorted = o;     o += align256(n * sizeof(PvObj));
-        part = o;       o += align256((size_t)PV_GRID * (size_t)binnr * 24);
-        total = o;
-    }
-};
+inline GridLayout pv_layout(size_t n, int binnr) {
+    return GridLayout(1, n, 0, grid_cells_cap(n, 1), sizeof(PvObj), (size_t)PV_GRID * (size_t)binnr * 24);
+}
 
 // One thread per object: r (widened to fp64), u = r / |r|, and the cartesian transverse velocity
 // t = J(th = theta2, ph = theta1)^T (0, v1, v2) of get_sph_to_cart_jacobian (or v itself when 3 components are given).
 // angle_mode 0: theta1 = arctan(x / z), theta2 = arctan(y / z), both + 10 deg; 1: given in radians; 2: given in degrees.
-// The bounding box of r goes to prm->kmin / kmax, one atomic per workgroup and axis.
+// The bounding box of r goes to `box` (grid_bounds_commit).
 template <typename TP, typename TV>
 __global__ void __launch_bounds__(256)
 pv_prep_kernel(const TP* __restrict__ pos, const TV* __restrict__ vel, int vel_ncomp, const double* __restrict__ th1,
-               const double* __restrict__ th2, int angle_mode, size_t n, PvObj* __restrict__ obj, PvParams* prm) {
-    __shared__ double wlo[3][4], whi[3][4];
+               const double* __restrict__ th2, int angle_mode, size_t n, PvObj* __restrict__ obj, GridBounds* box) {
     double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
@@ -79,30 +60,15 @@ pv_prep_kernel(const TP* __restrict__ pos, const TV* __restrict__ vel, int vel_n
         obj[i] = o;
         for (int a = 0; a < 3; ++a) { lo[a] = fmin(lo[a], o.r[a]); hi[a] = fmax(hi[a], o.r[a]); }
     }
-    const int w = threadIdx.x / 64, l = threadIdx.x % 64;
-    for (int a = 0; a < 3; ++a) {
-        const double mn = wave_min(lo[a]), mx = wave_max(hi[a]);
-        if (l == 0) { wlo[a][w] = mn; whi[a][w] = mx; }
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const int a = threadIdx.x;
-        double mn = wlo[a][0], mx = whi[a][0];
-        for (int k = 1; k < 4; ++k) { mn = fmin(mn, wlo[a][k]); mx = fmax(mx, whi[a][k]); }
-        if (mn <= mx) {
-            atomicMin(&prm->kmin[a], d2key(mn));
-            atomicMax(&prm->kmax[a], d2key(mx));
-        }
-    }
+    grid_bounds_commit<256>(lo, hi, box);
 }
 
-// Work item = (tile of PV_BLOCK objects of cell a, neighbour k): each thread holds one i of the tile, the j objects of
-// cell a + offset[k] pass through LDS PV_BLOCK at a time (k = 0: the cell itself, j > i only).  A persistent grid walks
-// the items with a fixed stride; each wave adds into its own LDS histogram (nom, denom, pairs), and at the end the
-// workgroup's row (waves summed in order) is stored to part - no global atomics.
+// The walk of cell_grid.h (grid_pair_walk: one set, open boundaries) with r, u, t of the staged j objects in LDS.  Each
+// wave adds into its own LDS histogram (nom, denom, pairs), and at the end the workgroup's row (waves summed in order)
+// is stored to part - no global atomics.
 __global__ void __launch_bounds__(PV_BLOCK)
 pv_pair_kernel(const PvObj* __restrict__ sorted, const unsigned* __restrict__ cell_start,
-               const unsigned* __restrict__ tile_start, const PvParams* prm, int binnr, double binwidth,
+               const unsigned* __restrict__ tile_start, const GridBoxParams* prm, int binnr, double binwidth,
                double reach2, double* __restrict__ part) {
     extern __shared__ double lds[];
     double* jr = lds;                                   // [9][PV_BLOCK]: r, u, t of the staged j objects
@@ -115,112 +81,48 @@ pv_pair_kernel(const PvObj* __restrict__ sorted, const unsigned* __restrict__ ce
     double* whd = hd + w * binnr;
     unsigned long long* whc = hc + w * binnr;
 
-    const int dx = prm->dims[0], dy = prm->dims[1], dz = prm->dims[2];
-    const unsigned ncells = prm->ncells;
-    const unsigned long long nitems = (unsigned long long)prm->ntiles * GRID_NEIGH;
-    for (unsigned long long item = blockIdx.x; item < nitems; item += gridDim.x) {
-        const unsigned tile = (unsigned)(item / GRID_NEIGH);
-        const int k = (int)(item % GRID_NEIGH);
-        const unsigned a = grid_cell_of_tile(tile_start, ncells, tile);
-        const int ax = (int)(a % (unsigned)dx), ay = (int)((a / (unsigned)dx) % (unsigned)dy), az = (int)(a / ((unsigned)dx * (unsigned)dy));
-        const int bx = ax + grid_offsets[k][0], by = ay + grid_offsets[k][1], bz = az + grid_offsets[k][2];
-        if (bx < 0 || bx >= dx || by < 0 || by >= dy || bz < 0 || bz >= dz) continue;
-        const unsigned b = ((unsigned)bz * (unsigned)dy + (unsigned)by) * (unsigned)dx + (unsigned)bx;
-        const unsigned i0 = cell_start[a] + (tile - tile_start[a]) * PV_BLOCK;
-        const unsigned i1 = min(i0 + PV_BLOCK, cell_start[a + 1]);
-        const unsigned j0 = k == 0 ? i0 + 1 : cell_start[b];
-        const unsigned j1 = cell_start[b + 1];
-        if (j0 >= j1) continue;
-
-        const unsigned i = i0 + tid;
-        const bool valid = i < i1;
-        PvObj oi;
-        if (valid) oi = sorted[i];
-        for (unsigned jc = j0; jc < j1; jc += PV_BLOCK) {
-            __syncthreads();
-            if (jc + tid < j1) {
-                const PvObj oj = sorted[jc + tid];
-                for (int c = 0; c < 3; ++c) {
-                    jr[c * PV_BLOCK + tid] = oj.r[c];
-                    jr[(3 + c) * PV_BLOCK + tid] = oj.u[c];
-                    jr[(6 + c) * PV_BLOCK + tid] = oj.t[c];
-                }
+    PvObj oi;
+    grid_pair_walk<PV_BLOCK>(
+        cell_start, tile_start, cell_start, prm, false, true,
+        [&](unsigned i) { oi = sorted[i]; },
+        [](unsigned, int) {},
+        [&](unsigned j, int t) {
+            const PvObj oj = sorted[j];
+            for (int c = 0; c < 3; ++c) {
+                jr[c * PV_BLOCK + t] = oj.r[c];
+                jr[(3 + c) * PV_BLOCK + t] = oj.u[c];
+                jr[(6 + c) * PV_BLOCK + t] = oj.t[c];
             }
-            __syncthreads();
-            if (!valid) continue;
-            const int m = (int)min((unsigned)PV_BLOCK, j1 - jc);
-            const int q0 = (k == 0 && i + 1 > jc) ? (int)min((unsigned)m, i + 1 - jc) : 0;
-            for (int q = q0; q < m; ++q) {
-                const double ddx = oi.r[0] - jr[q], ddy = oi.r[1] - jr[PV_BLOCK + q], ddz = oi.r[2] - jr[2 * PV_BLOCK + q];
-                const double d2 = (ddx * ddx + ddy * ddy) + ddz * ddz;
-                if (!(d2 <= reach2)) continue;
-                const double d = sqrt(d2);
-                const int bin = (int)(d / binwidth);
-                if (bin >= binnr) continue;
-                const double px = ddx / d, py = ddy / d, pz = ddz / d;
-                const double ujx = jr[3 * PV_BLOCK + q], ujy = jr[4 * PV_BLOCK + q], ujz = jr[5 * PV_BLOCK + q];
-                const double pi_ = (px * oi.u[0] + py * oi.u[1]) + pz * oi.u[2];
-                const double pj_ = (px * ujx + py * ujy) + pz * ujz;
-                const double qx = 0.5 * ((2.0 * px - oi.u[0] * pi_) - ujx * pj_);
-                const double qy = 0.5 * ((2.0 * py - oi.u[1] * pi_) - ujy * pj_);
-                const double qz = 0.5 * ((2.0 * pz - oi.u[2] * pi_) - ujz * pj_);
-                const double tx = oi.t[0] - jr[6 * PV_BLOCK + q], ty = oi.t[1] - jr[7 * PV_BLOCK + q],
-                             tz = oi.t[2] - jr[8 * PV_BLOCK + q];
-                atomicAdd(&whn[bin], (tx * qx + ty * qy) + tz * qz);
-                atomicAdd(&whd[bin], (qx * qx + qy * qy) + qz * qz);
-                atomicAdd(&whc[bin], 1ull);
-            }
-        }
-    }
+        },
+        [&](int q) {
+            const double ddx = oi.r[0] - jr[q], ddy = oi.r[1] - jr[PV_BLOCK + q], ddz = oi.r[2] - jr[2 * PV_BLOCK + q];
+            const double d2 = (ddx * ddx + ddy * ddy) + ddz * ddz;
+            if (!(d2 <= reach2)) return;
+            const double d = sqrt(d2);
+            const int bin = (int)(d / binwidth);
+            if (bin >= binnr) return;
+            const double px = ddx / d, py = ddy / d, pz = ddz / d;
+            const double ujx = jr[3 * PV_BLOCK + q], ujy = jr[4 * PV_BLOCK + q], ujz = jr[5 * PV_BLOCK + q];
+            const double pi_ = (px * oi.u[0] + py * oi.u[1]) + pz * oi.u[2];
+            const double pj_ = (px * ujx + py * ujy) + pz * ujz;
+            const double qx = 0.5 * ((2.0 * px - oi.u[0] * pi_) - ujx * pj_);
+            const double qy = 0.5 * ((2.0 * py - oi.u[1] * pi_) - ujy * pj_);
+            const double qz = 0.5 * ((2.0 * pz - oi.u[2] * pi_) - ujz * pj_);
+            const double tx = oi.t[0] - jr[6 * PV_BLOCK + q], ty = oi.t[1] - jr[7 * PV_BLOCK + q],
+                         tz = oi.t[2] - jr[8 * PV_BLOCK + q];
+            atomicAdd(&whn[bin], (tx * qx + ty * qy) + tz * qz);
+            atomicAdd(&whd[bin], (qx * qx + qy * qy) + qz * qz);
+            atomicAdd(&whc[bin], 1ull);
+        });
     __syncthreads();
-    double* pn = part;
-    double* pd = part + (size_t)PV_GRID * binnr;
-    unsigned long long* pc = (unsigned long long*)(part + 2 * (size_t)PV_GRID * binnr);
-    for (int bin = tid; bin < binnr; bin += PV_BLOCK) {
-        double sn = hn[bin], sd = hd[bin];
-        unsigned long long sc = hc[bin];
-        for (int v = 1; v < PV_WAVES; ++v) { sn += hn[v * binnr + bin]; sd += hd[v * binnr + bin]; sc += hc[v * binnr + bin]; }
-        const size_t o = (size_t)blockIdx.x * binnr + bin;
-        pn[o] = sn;
-        pd[o] = sd;
-        pc[o] = sc;
-    }
-}
-
-// out[bin] = sum of the PV_GRID workgroup rows, in row order.
-__global__ void __launch_bounds__(256)
-pv_reduce_kernel(const double* __restrict__ part, int binnr, double* __restrict__ nom, double* __restrict__ denom,
-                 unsigned long long* __restrict__ counts) {
-    const int bin = blockIdx.x * blockDim.x + threadIdx.x;
-    if (bin >= binnr) return;
-    const double* pn = part;
-    const double* pd = part + (size_t)PV_GRID * binnr;
-    const unsigned long long* pc = (const unsigned long long*)(part + 2 * (size_t)PV_GRID * binnr);
-    double sn = 0.0, sd = 0.0;
-    unsigned long long sc = 0;
-    for (int g = 0; g < PV_GRID; ++g) {
-        const size_t o = (size_t)g * binnr + bin;
-        sn += pn[o];
-        sd += pd[o];
-        sc += pc[o];
-    }
-    nom[bin] = sn;
-    denom[bin] = sd;
-    counts[bin] = sc;
-}
-
-template <typename TP, typename TV>
-void launch_prep(const void* pos, const void* vel, int vel_ncomp, const double* th1, const double* th2, int angle_mode,
-                 size_t n, PvObj* obj, PvParams* prm, hipStream_t s) {
-    pv_prep_kernel<TP, TV><<<ast::stream_grid(n, 256), 256, 0, s>>>((const TP*)pos, (const TV*)vel, vel_ncomp, th1, th2,
-                                                                     angle_mode, n, obj, prm);
+    grid_store_rows<PV_WAVES, PV_GRID>(hn, hd, hc, binnr, part);
 }
 
 }  // namespace
 
 extern "C" size_t ast_pairwise_workspace_bytes(size_t n, int binnr) {
     if (binnr < 1 || binnr > PV_MAX_BINS) return 0;
-    return PvLayout(n, binnr).total;
+    return pv_layout(n, binnr).total;
 }
 
 extern "C" int ast_pairwise_max_bins(void) { return PV_MAX_BINS; }
@@ -235,24 +137,21 @@ extern "C" int ast_pairwise_tv_prepare(const void* pos_d, int pos_dtype, const v
     AST_CHECK_ARG(angle_mode == 0 || vel_ncomp == 3 || n == 0 || (theta1_d && theta2_d));
     AST_CHECK_ARG(n < (size_t(1) << 31));
     AST_CHECK_ARG(n == 0 || (pos_d && vel_d));
-    AST_CHECK_ARG(work_d && work_bytes >= PvLayout(n, 1).obj + align256(n * sizeof(PvObj)));
+    const GridLayout L = pv_layout(n, 1);
+    AST_CHECK_ARG(work_d && work_bytes >= L.sorted[0]);
     hipStream_t s = ast::as_stream(stream);
-    const PvLayout L(n, 1);
     char* ws = (char*)work_d;
-    PvParams* prm = (PvParams*)(ws + L.params);
-    AST_CHECK_HIP(hipMemsetAsync(prm->kmin, 0xff, sizeof(prm->kmin), s));
-    AST_CHECK_HIP(hipMemsetAsync(prm->kmax, 0x00, sizeof(prm->kmax), s));
+    GridBounds* box = (GridBounds*)(ws + L.bounds[0]);
+    if (int rc = grid_bounds_reset(box, s)) return rc;
     if (n == 0) return AST_OK;
     AST_PROF("pairwise_prep", s);
-    PvObj* obj = (PvObj*)(ws + L.obj);
-    if (pos_dtype == AST_F32 && vel_dtype == AST_F32)
-        launch_prep<float, float>(pos_d, vel_d, vel_ncomp, theta1_d, theta2_d, angle_mode, n, obj, prm, s);
-    else if (pos_dtype == AST_F32)
-        launch_prep<float, double>(pos_d, vel_d, vel_ncomp, theta1_d, theta2_d, angle_mode, n, obj, prm, s);
-    else if (vel_dtype == AST_F32)
-        launch_prep<double, float>(pos_d, vel_d, vel_ncomp, theta1_d, theta2_d, angle_mode, n, obj, prm, s);
-    else
-        launch_prep<double, double>(pos_d, vel_d, vel_ncomp, theta1_d, theta2_d, angle_mode, n, obj, prm, s);
+    PvObj* obj = (PvObj*)(ws + L.obj[0]);
+    ast::dispatch_f32_f64(pos_dtype == AST_F32, vel_dtype == AST_F32, [&](auto tp, auto tv) {
+        using TP = decltype(tp);
+        using TV = decltype(tv);
+        pv_prep_kernel<TP, TV><<<ast::stream_grid(n, 256), 256, 0, s>>>(
+            (const TP*)pos_d, (const TV*)vel_d, vel_ncomp, theta1_d, theta2_d, angle_mode, n, obj, box);
+    });
     AST_CHECK_LAUNCH();
     return AST_OK;
 }
@@ -271,30 +170,19 @@ extern "C" int ast_pairwise_tv(void* work_d, size_t work_bytes, size_t n, int bi
         AST_CHECK_HIP(hipMemsetAsync(counts_d, 0, binnr * sizeof(unsigned long long), s));
         return AST_OK;
     }
-    const PvLayout L(n, binnr);
+    const GridLayout L = pv_layout(n, binnr);
     char* ws = (char*)work_d;
-    PvParams* prm = (PvParams*)(ws + L.params);
-    unsigned* cnt = (unsigned*)(ws + L.cnt);
-    unsigned* cell_start = (unsigned*)(ws + L.cell_start);
-    unsigned* tile_start = (unsigned*)(ws + L.tile_start);
-    unsigned* cursor = (unsigned*)(ws + L.cursor);
-    unsigned* cell_of = (unsigned*)(ws + L.cell_of);
-    const PvObj* obj = (const PvObj*)(ws + L.obj);
-    PvObj* sorted = (PvObj*)(ws + L.sorted);
+    GridBoxParams* prm = (GridBoxParams*)(ws + L.grid);
+    const unsigned* cell_start = (const unsigned*)(ws + L.cell_start[0]);
+    const unsigned* tile_start = (const unsigned*)(ws + L.tile_start[0]);
+    const PvObj* sorted = (const PvObj*)(ws + L.sorted[0]);
     double* part = (double*)(ws + L.part);
-    const size_t cap = cells_cap(n);
     const double rmax = (double)binnr * binwidth;
     {
         AST_PROF("pairwise_grid", s);
-        grid_box_plan_kernel<<<1, 64, 0, s>>>(prm, rmax, (unsigned)cap, single_cell);
+        grid_box_plan_kernel<<<1, 64, 0, s>>>(prm, rmax, (unsigned)L.cap, single_cell);
         AST_CHECK_LAUNCH();
-        AST_CHECK_HIP(hipMemsetAsync(cnt, 0, cap * 4, s));
-        grid_box_count_kernel<<<ast::stream_grid(n, 256), 256, 0, s>>>(obj, n, prm, cell_of, cnt);
-        AST_CHECK_LAUNCH();
-        grid_scan_kernel<PV_BLOCK><<<1, 1024, 0, s>>>(cnt, prm, cell_start, tile_start, cursor);
-        AST_CHECK_LAUNCH();
-        grid_scatter_kernel<<<ast::stream_grid(n, 256), 256, 0, s>>>(obj, n, cell_of, cursor, sorted);
-        AST_CHECK_LAUNCH();
+        if (int rc = grid_sort_set<PV_BLOCK, PvObj>(ws, L, 0, n, s)) return rc;
     }
     // Pre-test on d^2 with a relative margin far above the rounding of d and d / binwidth: every pair whose
     // int(d / binwidth) < binnr passes it; the bin decision itself is the fp64 int(d / binwidth) < binnr.
@@ -307,7 +195,7 @@ extern "C" int ast_pairwise_tv(void* work_d, size_t work_bytes, size_t n, int bi
     }
     {
         AST_PROF("pairwise_reduce", s);
-        pv_reduce_kernel<<<(binnr + 255) / 256, 256, 0, s>>>(part, binnr, nom_d, denom_d, counts_d);
+        grid_reduce3_kernel<PV_GRID><<<(binnr + 255) / 256, 256, 0, s>>>(part, binnr, nom_d, denom_d, counts_d);
         AST_CHECK_LAUNCH();
     }
     return AST_OK;

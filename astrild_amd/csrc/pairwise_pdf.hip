@@ -25,31 +25,15 @@ constexpr unsigned long long PD_FLUSH_AT = 0xffffffffull;        // 32-bit LDS c
 
 struct PdObj { double r[3], v[3]; unsigned idx, pad; };
 
-using PdParams = GridBoxParams;
-
 struct PdBins {
     int kind, dist_bin, vel_bin, moments;
     double reach, reach2, dist_width, vel_width, offset;
     unsigned first, second;
 };
 
-struct PdLayout {
-    size_t params, cnt, cell_start, tile_start, cursor, cell_of, obj, sorted, part, total;
-    PdLayout(size_t n, int moment_rows) {
-        const size_t cap = grid_box_cells_cap(n);
-        size_t o = 0;
-        params = o;     o += align256(sizeof(PdParams));
-        cnt = o;        o += align256(cap * 4);
-        cell_start = o; o += align256((cap + 1) * 4);
-        tile_start = o; o += align256((cap + 1) * 4);
-        cursor = o;     o += align256(cap * 4);
-        cell_of = o;    o += align256(n * 4);
-        obj = o;        o += align256(n * sizeof(PdObj));
-        sorted = o;     o += align256(n * sizeof(PdObj));
-        part = o;       o += align256((size_t)PD_GRID * (size_t)moment_rows * 24);
-        total = o;
-    }
-};
+inline GridLayout pd_layout(size_t n, int moment_rows) {
+    return GridLayout(1, n, 0, grid_cells_cap(n, 1), sizeof(PdObj), (size_t)PD_GRID * (size_t)moment_rows * 24);
+}
 
 inline bool bins_ok(int dist_bin, int vel_bin, int moments) {
     return dist_bin >= 1 && vel_bin >= 1 && (long long)dist_bin * vel_bin <= PD_MAX_BINS &&
@@ -68,13 +52,12 @@ inline int lds_bins(int dist_bin, int moments) {
     return PD_LDS_BUDGET > fixed ? (int)((PD_LDS_BUDGET - fixed) / 4) : 0;
 }
 
-// One thread per object: r and v widened to fp64, the original index, and the bounding box of r to prm->kmin / kmax
-// (one atomic per workgroup and axis).
+// One thread per object: r and v widened to fp64, the original index, and the bounding box of r to `box`
+// (grid_bounds_commit).
 template <typename TP, typename TV>
 __global__ void __launch_bounds__(256)
 pd_prep_kernel(const TP* __restrict__ pos, const TV* __restrict__ vel, size_t n, PdObj* __restrict__ obj,
-               PdParams* prm) {
-    __shared__ double wlo[3][4], whi[3][4];
+               GridBounds* box) {
     double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
@@ -85,26 +68,11 @@ pd_prep_kernel(const TP* __restrict__ pos, const TV* __restrict__ vel, size_t n,
         obj[i] = o;
         for (int a = 0; a < 3; ++a) { lo[a] = fmin(lo[a], o.r[a]); hi[a] = fmax(hi[a], o.r[a]); }
     }
-    const int w = threadIdx.x / 64, l = threadIdx.x % 64;
-    for (int a = 0; a < 3; ++a) {
-        const double mn = wave_min(lo[a]), mx = wave_max(hi[a]);
-        if (l == 0) { wlo[a][w] = mn; whi[a][w] = mx; }
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const int a = threadIdx.x;
-        double mn = wlo[a][0], mx = whi[a][0];
-        for (int k = 1; k < 4; ++k) { mn = fmin(mn, wlo[a][k]); mx = fmax(mx, whi[a][k]); }
-        if (mn <= mx) {
-            atomicMin(&prm->kmin[a], d2key(mn));
-            atomicMax(&prm->kmax[a], d2key(mx));
-        }
-    }
+    grid_bounds_commit<256>(lo, hi, box);
 }
 
-// Work item = (tile of PD_BLOCK objects of cell a, neighbour k), walked by a persistent grid as in pairwise.hip: each
-// thread holds one i of the tile, the j objects of cell a + offset[k] pass through LDS PD_BLOCK at a time as rows r, v
-// and original index (k = 0: the cell itself, j > i only).  A pair is seen when d = sqrt((dx dx + dy dy) + dz dz)
+// The walk of cell_grid.h (grid_pair_walk: one set, open boundaries) with the staged j objects in LDS as rows r, v and
+// original index.  A pair is seen when d = sqrt((dx dx + dy dy) + dz dz)
 // <= reach and the smaller of its two original indices lies in [first, second).  With the differences taken j - i,
 //   kind 0 (z_sign): v12 = (vz_j - vz_i) sign(z_j - z_i),   kind 1 (radial): v12 = ((dvx dx + dvy dy) + dvz dz) / d;
 // both are unchanged bit for bit when i and j swap (two exact negations per product), so which of the two the thread
@@ -120,7 +88,7 @@ pd_prep_kernel(const TP* __restrict__ pos, const TV* __restrict__ vel, size_t n,
 template <bool LDS_HIST>
 __global__ void __launch_bounds__(PD_BLOCK)
 pd_pair_kernel(const PdObj* __restrict__ sorted, const unsigned* __restrict__ cell_start,
-               const unsigned* __restrict__ tile_start, const PdParams* prm, PdBins bn, unsigned long long flush_at,
+               const unsigned* __restrict__ tile_start, const GridBoxParams* prm, PdBins bn, unsigned long long flush_at,
                unsigned long long* __restrict__ hist_g, unsigned long long* __restrict__ outside_g,
                double* __restrict__ part) {
     extern __shared__ double lds[];
@@ -156,132 +124,71 @@ pd_pair_kernel(const PdObj* __restrict__ sorted, const unsigned* __restrict__ ce
     };
 
     const float fdist = (float)bn.dist_bin, fvel = (float)bn.vel_bin;
-    const int dx = prm->dims[0], dy = prm->dims[1], dz = prm->dims[2];
-    const unsigned ncells = prm->ncells;
-    const unsigned long long nitems = (unsigned long long)prm->ntiles * GRID_NEIGH;
-    for (unsigned long long item = blockIdx.x; item < nitems; item += gridDim.x) {
-        const unsigned tile = (unsigned)(item / GRID_NEIGH);
-        const int k = (int)(item % GRID_NEIGH);
-        const unsigned a = grid_cell_of_tile(tile_start, ncells, tile);
-        const int ax = (int)(a % (unsigned)dx), ay = (int)((a / (unsigned)dx) % (unsigned)dy), az = (int)(a / ((unsigned)dx * (unsigned)dy));
-        const int bx = ax + grid_offsets[k][0], by = ay + grid_offsets[k][1], bz = az + grid_offsets[k][2];
-        if (bx < 0 || bx >= dx || by < 0 || by >= dy || bz < 0 || bz >= dz) continue;
-        const unsigned b = ((unsigned)bz * (unsigned)dy + (unsigned)by) * (unsigned)dx + (unsigned)bx;
-        const unsigned i0 = cell_start[a] + (tile - tile_start[a]) * PD_BLOCK;
-        const unsigned i1 = min(i0 + PD_BLOCK, cell_start[a + 1]);
-        const unsigned j0 = k == 0 ? i0 + 1 : cell_start[b];
-        const unsigned j1 = cell_start[b + 1];
-        if (j0 >= j1) continue;
-
-        const unsigned i = i0 + tid;
-        const bool valid = i < i1;
-        PdObj oi;
-        if (valid) oi = sorted[i];
-        for (unsigned jc = j0; jc < j1; jc += PD_BLOCK) {
-            const int m = (int)min((unsigned)PD_BLOCK, j1 - jc);
+    PdObj oi;
+    grid_pair_walk<PD_BLOCK>(
+        cell_start, tile_start, cell_start, prm, false, true,
+        [&](unsigned i) { oi = sorted[i]; },
+        [&](unsigned ni, int m) {
             if (LDS_HIST) {
-                const unsigned long long stage = (unsigned long long)(i1 - i0) * (unsigned long long)m;
+                const unsigned long long stage = (unsigned long long)ni * (unsigned long long)m;
                 if (pending + stage > flush_at) flush();
                 pending += stage;
             }
-            __syncthreads();
-            if (jc + tid < j1) {
-                const PdObj oj = sorted[jc + tid];
-                for (int c = 0; c < 3; ++c) {
-                    jr[c * PD_BLOCK + tid] = oj.r[c];
-                    jr[(3 + c) * PD_BLOCK + tid] = oj.v[c];
-                }
-                jidx[tid] = oj.idx;
+        },
+        [&](unsigned j, int t) {
+            const PdObj oj = sorted[j];
+            for (int c = 0; c < 3; ++c) {
+                jr[c * PD_BLOCK + t] = oj.r[c];
+                jr[(3 + c) * PD_BLOCK + t] = oj.v[c];
             }
-            __syncthreads();
-            if (!valid) continue;
-            const int q0 = (k == 0 && i + 1 > jc) ? (int)min((unsigned)m, i + 1 - jc) : 0;
-            for (int q = q0; q < m; ++q) {
-                const double ddx = jr[q] - oi.r[0], ddy = jr[PD_BLOCK + q] - oi.r[1], ddz = jr[2 * PD_BLOCK + q] - oi.r[2];
-                const double d2 = (ddx * ddx + ddy * ddy) + ddz * ddz;
-                if (!(d2 <= bn.reach2)) continue;
-                const double d = sqrt(d2);
-                if (!(d <= bn.reach)) continue;
-                const unsigned row = min(oi.idx, jidx[q]);
-                if (row < bn.first || row >= bn.second) continue;
-                const double wz = jr[5 * PD_BLOCK + q] - oi.v[2];
-                double v12;
-                if (bn.kind == 0) {
-                    v12 = wz * (double)((int)(ddz > 0.0) - (int)(ddz < 0.0));
-                } else {
-                    const double wx = jr[3 * PD_BLOCK + q] - oi.v[0], wy = jr[4 * PD_BLOCK + q] - oi.v[1];
-                    v12 = ((wx * ddx + wy * ddy) + wz * ddz) / d;
-                }
-                const float ds = (float)(d / bn.dist_width);
-                const float vs = (float)(v12 / bn.vel_width + bn.offset);
-                const bool in_rows = ds < fdist;
-                const int ra = in_rows ? (int)ds : 0;
-                if (in_rows && vs >= 0.0f && vs < fvel) {
-                    const int bin = ra * bn.vel_bin + (int)vs;
-                    if (LDS_HIST) atomicAdd(&hist[bin], 1u);
-                    else atomicAdd(&hist_g[bin], 1ull);
-                } else {
-                    ++outside;
-                }
-                if (mrows && in_rows && isfinite(v12)) {
-                    atomicAdd(&wh1[ra], v12);
-                    atomicAdd(&wh2[ra], v12 * v12);
-                    atomicAdd(&whc[ra], 1ull);
-                }
+            jidx[t] = oj.idx;
+        },
+        [&](int q) {
+            const double ddx = jr[q] - oi.r[0], ddy = jr[PD_BLOCK + q] - oi.r[1], ddz = jr[2 * PD_BLOCK + q] - oi.r[2];
+            const double d2 = (ddx * ddx + ddy * ddy) + ddz * ddz;
+            if (!(d2 <= bn.reach2)) return;
+            const double d = sqrt(d2);
+            if (!(d <= bn.reach)) return;
+            const unsigned row = min(oi.idx, jidx[q]);
+            if (row < bn.first || row >= bn.second) return;
+            const double wz = jr[5 * PD_BLOCK + q] - oi.v[2];
+            double v12;
+            if (bn.kind == 0) {
+                v12 = wz * (double)((int)(ddz > 0.0) - (int)(ddz < 0.0));
+            } else {
+                const double wx = jr[3 * PD_BLOCK + q] - oi.v[0], wy = jr[4 * PD_BLOCK + q] - oi.v[1];
+                v12 = ((wx * ddx + wy * ddy) + wz * ddz) / d;
             }
-        }
-    }
+            const float ds = (float)(d / bn.dist_width);
+            const float vs = (float)(v12 / bn.vel_width + bn.offset);
+            const bool in_rows = ds < fdist;
+            const int ra = in_rows ? (int)ds : 0;
+            if (in_rows && vs >= 0.0f && vs < fvel) {
+                const int bin = ra * bn.vel_bin + (int)vs;
+                if (LDS_HIST) atomicAdd(&hist[bin], 1u);
+                else atomicAdd(&hist_g[bin], 1ull);
+            } else {
+                ++outside;
+            }
+            if (mrows && in_rows && isfinite(v12)) {
+                atomicAdd(&wh1[ra], v12);
+                atomicAdd(&wh2[ra], v12 * v12);
+                atomicAdd(&whc[ra], 1ull);
+            }
+        });
     if (LDS_HIST) flush();
     for (int o = 32; o > 0; o >>= 1) outside += __shfl_xor(outside, o, 64);
     if (tid % 64 == 0 && outside) atomicAdd(outside_g, outside);
     if (!mrows) return;
     __syncthreads();
-    double* p1 = part;
-    double* p2 = part + (size_t)PD_GRID * mrows;
-    unsigned long long* pc = (unsigned long long*)(part + 2 * (size_t)PD_GRID * mrows);
-    for (int bin = tid; bin < mrows; bin += PD_BLOCK) {
-        double s1 = h1[bin], s2 = h2[bin];
-        unsigned long long sc = hc[bin];
-        for (int v = 1; v < PD_WAVES; ++v) { s1 += h1[v * mrows + bin]; s2 += h2[v * mrows + bin]; sc += hc[v * mrows + bin]; }
-        const size_t o = (size_t)blockIdx.x * mrows + bin;
-        p1[o] = s1;
-        p2[o] = s2;
-        pc[o] = sc;
-    }
-}
-
-// out[bin] = sum of the PD_GRID workgroup rows, in row order.
-__global__ void __launch_bounds__(256)
-pd_reduce_kernel(const double* __restrict__ part, int mrows, double* __restrict__ s1, double* __restrict__ s2,
-                 unsigned long long* __restrict__ counts) {
-    const int bin = blockIdx.x * blockDim.x + threadIdx.x;
-    if (bin >= mrows) return;
-    const double* p1 = part;
-    const double* p2 = part + (size_t)PD_GRID * mrows;
-    const unsigned long long* pc = (const unsigned long long*)(part + 2 * (size_t)PD_GRID * mrows);
-    double a1 = 0.0, a2 = 0.0;
-    unsigned long long sc = 0;
-    for (int g = 0; g < PD_GRID; ++g) {
-        const size_t o = (size_t)g * mrows + bin;
-        a1 += p1[o];
-        a2 += p2[o];
-        sc += pc[o];
-    }
-    s1[bin] = a1;
-    s2[bin] = a2;
-    counts[bin] = sc;
-}
-
-template <typename TP, typename TV>
-void launch_prep(const void* pos, const void* vel, size_t n, PdObj* obj, PdParams* prm, hipStream_t s) {
-    pd_prep_kernel<TP, TV><<<ast::stream_grid(n, 256), 256, 0, s>>>((const TP*)pos, (const TV*)vel, n, obj, prm);
+    grid_store_rows<PD_WAVES, PD_GRID>(h1, h2, hc, mrows, part);
 }
 
 }  // namespace
 
 extern "C" size_t ast_pairwise_pdf_workspace_bytes(size_t n, int dist_bin, int vel_bin, int moments) {
     if (!bins_ok(dist_bin, vel_bin, moments)) return 0;
-    return PdLayout(n, moments ? dist_bin : 0).total;
+    return pd_layout(n, moments ? dist_bin : 0).total;
 }
 
 extern "C" int ast_pairwise_pdf_max_bins(void) { return PD_MAX_BINS; }
@@ -297,24 +204,20 @@ extern "C" int ast_pairwise_pdf_prepare(const void* pos_d, int pos_dtype, const 
     AST_CHECK_ARG(vel_dtype == AST_F32 || vel_dtype == AST_F64);
     AST_CHECK_ARG(n < (size_t(1) << 31));
     AST_CHECK_ARG(n == 0 || (pos_d && vel_d));
-    const PdLayout L(n, 0);
-    AST_CHECK_ARG(work_d && work_bytes >= L.obj + align256(n * sizeof(PdObj)));
+    const GridLayout L = pd_layout(n, 0);
+    AST_CHECK_ARG(work_d && work_bytes >= L.sorted[0]);
     hipStream_t s = ast::as_stream(stream);
     char* ws = (char*)work_d;
-    PdParams* prm = (PdParams*)(ws + L.params);
-    AST_CHECK_HIP(hipMemsetAsync(prm->kmin, 0xff, sizeof(prm->kmin), s));
-    AST_CHECK_HIP(hipMemsetAsync(prm->kmax, 0x00, sizeof(prm->kmax), s));
+    GridBounds* box = (GridBounds*)(ws + L.bounds[0]);
+    if (int rc = grid_bounds_reset(box, s)) return rc;
     if (n == 0) return AST_OK;
     AST_PROF("pairwise_pdf_prep", s);
-    PdObj* obj = (PdObj*)(ws + L.obj);
-    if (pos_dtype == AST_F32 && vel_dtype == AST_F32)
-        launch_prep<float, float>(pos_d, vel_d, n, obj, prm, s);
-    else if (pos_dtype == AST_F32)
-        launch_prep<float, double>(pos_d, vel_d, n, obj, prm, s);
-    else if (vel_dtype == AST_F32)
-        launch_prep<double, float>(pos_d, vel_d, n, obj, prm, s);
-    else
-        launch_prep<double, double>(pos_d, vel_d, n, obj, prm, s);
+    PdObj* obj = (PdObj*)(ws + L.obj[0]);
+    ast::dispatch_f32_f64(pos_dtype == AST_F32, vel_dtype == AST_F32, [&](auto tp, auto tv) {
+        using TP = decltype(tp);
+        using TV = decltype(tv);
+        pd_prep_kernel<TP, TV><<<ast::stream_grid(n, 256), 256, 0, s>>>((const TP*)pos_d, (const TV*)vel_d, n, obj, box);
+    });
     AST_CHECK_LAUNCH();
     return AST_OK;
 }
@@ -348,29 +251,18 @@ extern "C" int ast_pairwise_pdf(void* work_d, size_t work_bytes, size_t n, int k
         }
         return AST_OK;
     }
-    const PdLayout L(n, moments ? dist_bin : 0);
+    const GridLayout L = pd_layout(n, moments ? dist_bin : 0);
     char* ws = (char*)work_d;
-    PdParams* prm = (PdParams*)(ws + L.params);
-    unsigned* cnt = (unsigned*)(ws + L.cnt);
-    unsigned* cell_start = (unsigned*)(ws + L.cell_start);
-    unsigned* tile_start = (unsigned*)(ws + L.tile_start);
-    unsigned* cursor = (unsigned*)(ws + L.cursor);
-    unsigned* cell_of = (unsigned*)(ws + L.cell_of);
-    const PdObj* obj = (const PdObj*)(ws + L.obj);
-    PdObj* sorted = (PdObj*)(ws + L.sorted);
+    GridBoxParams* prm = (GridBoxParams*)(ws + L.grid);
+    const unsigned* cell_start = (const unsigned*)(ws + L.cell_start[0]);
+    const unsigned* tile_start = (const unsigned*)(ws + L.tile_start[0]);
+    const PdObj* sorted = (const PdObj*)(ws + L.sorted[0]);
     double* part = (double*)(ws + L.part);
-    const size_t cap = grid_box_cells_cap(n);
     {
         AST_PROF("pairwise_pdf_grid", s);
-        grid_box_plan_kernel<<<1, 64, 0, s>>>(prm, reach, (unsigned)cap, single_cell);
+        grid_box_plan_kernel<<<1, 64, 0, s>>>(prm, reach, (unsigned)L.cap, single_cell);
         AST_CHECK_LAUNCH();
-        AST_CHECK_HIP(hipMemsetAsync(cnt, 0, cap * 4, s));
-        grid_box_count_kernel<<<ast::stream_grid(n, 256), 256, 0, s>>>(obj, n, prm, cell_of, cnt);
-        AST_CHECK_LAUNCH();
-        grid_scan_kernel<PD_BLOCK><<<1, 1024, 0, s>>>(cnt, prm, cell_start, tile_start, cursor);
-        AST_CHECK_LAUNCH();
-        grid_scatter_kernel<<<ast::stream_grid(n, 256), 256, 0, s>>>(obj, n, cell_of, cursor, sorted);
-        AST_CHECK_LAUNCH();
+        if (int rc = grid_sort_set<PD_BLOCK, PdObj>(ws, L, 0, n, s)) return rc;
     }
     PdBins bn;
     bn.kind = kind;
@@ -414,7 +306,7 @@ extern "C" int ast_pairwise_pdf(void* work_d, size_t work_bytes, size_t n, int k
     }
     if (moments) {
         AST_PROF("pairwise_pdf_reduce", s);
-        pd_reduce_kernel<<<(dist_bin + 255) / 256, 256, 0, s>>>(part, dist_bin, s1_d, s2_d, mcount_d);
+        grid_reduce3_kernel<PD_GRID><<<(dist_bin + 255) / 256, 256, 0, s>>>(part, dist_bin, s1_d, s2_d, mcount_d);
         AST_CHECK_LAUNCH();
     }
     return AST_OK;

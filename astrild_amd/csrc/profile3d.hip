@@ -28,10 +28,6 @@ constexpr int P3_SCAN_TILE = 2048;          // cells per workgroup of the scan: 
 
 struct P3Rec { double r[3], w, v[3], pad; };            // 64 bytes
 
-struct P3Params {
-    unsigned long long kmin[3], kmax[3];    // bounds of the positions as order-preserving keys
-};
-
 struct P3Grid { double lo[3], inv_cs[3]; int dims; };
 
 // params | obj (np records) | cnt, cell_start (+ 1), cursor (ncells each) | tile_sum (ncells / P3_SCAN_TILE) | cell_of (np) |
@@ -41,7 +37,7 @@ struct P3Layout {
     size_t params, obj, cnt, cell_start, tile_sum, cursor, cell_of, sorted, part_c, part_m, total;
     P3Layout(size_t np, size_t ncells, size_t n_part, int nbins, int nmom) {
         size_t o = 0;
-        params = o;     o += align256(sizeof(P3Params));
+        params = o;     o += align256(sizeof(GridBounds));
         obj = o;        o += align256(np * sizeof(P3Rec));
         cnt = o;        o += ncells ? align256(ncells * 4) : 0;
         cell_start = o; o += ncells ? align256((ncells + 1) * 4) : 0;
@@ -62,12 +58,10 @@ __device__ inline double p3_load(const void* p, int dtype, size_t i) {
 }
 
 // One thread per particle: the fp64 record (r, w, v), a missing weight 1 and a missing velocity 0; the min / max of the
-// positions (NaN counts as -inf / +inf) go to prm->kmin / kmax, one atomic per workgroup and axis (as tp_prep_kernel).
-// obj == nullptr: only the bounds.
+// positions (NaN counts as -inf / +inf) go to `box` (grid_bounds_commit).  obj == nullptr: only the bounds.
 __global__ void __launch_bounds__(256)
 p3_prep_kernel(const void* __restrict__ pos, int pos_dtype, const void* __restrict__ wgt, int w_dtype,
-               const void* __restrict__ vel, int vel_dtype, size_t n, P3Rec* __restrict__ obj, P3Params* prm) {
-    __shared__ double wlo[3][4], whi[3][4];
+               const void* __restrict__ vel, int vel_dtype, size_t n, P3Rec* __restrict__ obj, GridBounds* box) {
     double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
@@ -85,30 +79,7 @@ p3_prep_kernel(const void* __restrict__ pos, int pos_dtype, const void* __restri
             hi[a] = fmax(hi[a], v == v ? v : INFINITY);
         }
     }
-    const int w = threadIdx.x / 64, l = threadIdx.x % 64;
-    for (int a = 0; a < 3; ++a) {
-        const double mn = wave_min(lo[a]), mx = wave_max(hi[a]);
-        if (l == 0) { wlo[a][w] = mn; whi[a][w] = mx; }
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const int a = threadIdx.x;
-        double mn = wlo[a][0], mx = whi[a][0];
-        for (int k = 1; k < 4; ++k) { mn = fmin(mn, wlo[a][k]); mx = fmax(mx, whi[a][k]); }
-        if (mn <= mx) {
-            atomicMin(&prm->kmin[a], d2key(mn));
-            atomicMax(&prm->kmax[a], d2key(mx));
-        }
-    }
-}
-
-// bounds[0..2] = min, bounds[3..5] = max of the positions; (+inf, -inf) when there are no particles.
-__global__ void p3_bounds_kernel(const P3Params* prm, double* __restrict__ bounds) {
-    const int a = threadIdx.x;
-    if (a >= 3) return;
-    const unsigned long long kmn = prm->kmin[a], kmx = prm->kmax[a];
-    bounds[a] = kmn > kmx ? INFINITY : key2d(kmn);
-    bounds[3 + a] = kmn > kmx ? -INFINITY : key2d(kmx);
+    grid_bounds_commit<256>(lo, hi, box);
 }
 
 // Exclusive scan of the cell counts in three launches.  First: tile_sum[t] = the sum of the counts of cells
@@ -461,17 +432,16 @@ extern "C" int ast_profile3d_prepare(const void* pos_d, int pos_dtype, const voi
     AST_CHECK_ARG(work_d && work_bytes >= (bounds_only ? L.obj : L.cnt));
     hipStream_t s = ast::as_stream(stream);
     char* ws = (char*)work_d;
-    P3Params* prm = (P3Params*)(ws + L.params);
-    AST_CHECK_HIP(hipMemsetAsync(prm->kmin, 0xff, sizeof(prm->kmin), s));
-    AST_CHECK_HIP(hipMemsetAsync(prm->kmax, 0x00, sizeof(prm->kmax), s));
+    GridBounds* box = (GridBounds*)(ws + L.params);
+    if (int rc = grid_bounds_reset(box, s)) return rc;
     if (np > 0) {
         AST_PROF("profile3d_prep", s);
         p3_prep_kernel<<<ast::stream_grid(np, 256), 256, 0, s>>>(pos_d, pos_dtype, weights_d, weights_dtype, vel_d,
                                                                  vel_dtype, np, bounds_only ? nullptr : (P3Rec*)(ws + L.obj),
-                                                                 prm);
+                                                                 box);
         AST_CHECK_LAUNCH();
     }
-    p3_bounds_kernel<<<1, 64, 0, s>>>(prm, bounds_d);
+    grid_bounds_kernel<1><<<1, 64, 0, s>>>(box, nullptr, nullptr, bounds_d);
     AST_CHECK_LAUNCH();
     return AST_OK;
 }

@@ -18,7 +18,7 @@ HALF_SHELL = (
     (-1, 0, 1), (0, 0, 1), (1, 0, 1),
     (-1, 1, 1), (0, 1, 1), (1, 1, 1),
 )
-MAX_CELLS = 1 << 20                         # GRID_BOX_MAX_CELLS
+MAX_CELLS = 1 << 20                         # GRID_MAX_CELLS
 TILE = 256                                  # PV_BLOCK, PD_BLOCK: objects per tile of a cell
 
 
@@ -72,6 +72,51 @@ def plan(pos, reach, single=False, **variant):
     cells = v.astype(np.int64)
     cell_id = (cells[:, 2] * dims[1] + cells[:, 1]) * dims[0] + cells[:, 0]
     return Plan(lo=lo, inv_cs=inv_cs, dims=dims, steps=steps, cells=cells, cell_id=cell_id)
+
+
+def plan_periodic(pos, boxsize, reach, single=False):
+    """grid_periodic_plan and grid_box_cell of cell_grid.h for a catalogue in the cube [0, boxsize]^3, op by op in
+    float64: floor(L / (reach (1 + 1e-6))) cells per axis, at most 1024, lowered until the cube fits the cap
+    max(27, min(N, MAX_CELLS)), at least 3 or else one cell; lo = 0, inv_cs = d / L (0 for one cell)."""
+    pos = np.asarray(pos, dtype=np.float64)
+    boxsize = np.float64(boxsize)
+    cap = max(27, min(len(pos), MAX_CELLS))
+    d = 1
+    m = np.floor(boxsize / (np.float64(reach) * (1.0 + 1e-6)))
+    if not single and m >= 3.0:
+        d = 1024 if m > 1024.0 else int(m)
+        while d * d * d > cap:
+            d -= 1
+    dims = np.full(3, d, dtype=np.int64)
+    inv_cs = np.full(3, float(d) / boxsize if d > 1 else 0.0)
+    v = (pos - 0.0) * inv_cs
+    v = np.where(v >= 0.0, v, 0.0)
+    v = np.minimum(v, (dims - 1).astype(np.float64))
+    cells = v.astype(np.int64)
+    cell_id = (cells[:, 2] * dims[1] + cells[:, 1]) * dims[0] + cells[:, 0]
+    return Plan(lo=np.zeros(3), inv_cs=inv_cs, dims=dims, steps=0, cells=cells, cell_id=cell_id)
+
+
+# (top s edge, objects, single_cell) -> cells per axis, in a box of L = 100: too wide a reach for 3 cells; exactly 3;
+# 10 lowered to the cap of 300 cells; lowered to the least cap, max(27, N); one forced cell.
+PERIODIC_L = 100.0
+PERIODIC_CASES = {
+    "two_fit": (40.0, 300, False, 1),
+    "three_fit": (33.0, 300, False, 3),
+    "cap_300": (9.99, 300, False, 6),
+    "cap_30": (9.99, 30, False, 3),
+    "single": (9.99, 300, True, 1),
+}
+
+
+def parse_grid_params(head):
+    """``struct GridBoxParams`` of astrild_amd/csrc/cell_grid.h from the first 128 bytes (uint8) of a pair finder's
+    workspace, where GridLayout puts it: GridBounds box: unsigned long long kmin[3], kmax[3] (bytes 0-47);
+    double lo[3] (48), inv_cs[3] (72); int dims[3] (96); unsigned ncells (108), ntiles (112)."""
+    head = np.ascontiguousarray(head, dtype=np.uint8)
+    return dict(lo=head[48:72].view(np.float64), inv_cs=head[72:96].view(np.float64),
+                dims=head[96:108].view(np.int32), ncells=int(head[108:112].view(np.uint32)[0]),
+                ntiles=int(head[112:116].view(np.uint32)[0]))
 
 
 def tiles(p):

@@ -1,4 +1,4 @@
-"""GPU: the two pairwise-velocity kernels that keep their own copies of the cell-grid pair walk - pairwise.hip
+"""GPU: the two pairwise-velocity kernels that walk the bounding-box cell grid of cell_grid.h - pairwise.hip
 (ast_pairwise_tv_prepare / ast_pairwise_tv) and pairwise_pdf.hip (ast_pairwise_pdf_prepare / ast_pairwise_pdf) - on the
 degenerate catalogues of tests/pair_geometry.py: planes, lines, coincident objects, a cap-limited grid, a pair on each
 of the 13 half-shell offsets, two crowded neighbour cells, coordinates a million from the origin, float32 coordinates,
@@ -150,15 +150,9 @@ def test_pdf_against_oracle(name, kind, cells, monkeypatch):
 
 # ------------------------------------------------------------------ the planned grid is the intended one
 def read_grid_params(work):
-    """The head of a pair finder's workspace after a run: mirrors ``struct GridBoxParams`` of
-    astrild_amd/csrc/cell_grid.h (PvParams / PdParams, at offset 0 of PvLayout / PdLayout) -
-    unsigned long long kmin[3], kmax[3] (bytes 0-47); double lo[3] (48), inv_cs[3] (72); int dims[3] (96);
-    unsigned ncells (108), ntiles (112)."""
+    """The head of a pair finder's workspace after a run: ``struct GridBoxParams`` (pair_geometry.parse_grid_params)."""
     torch.cuda.synchronize()
-    head = work[:128].cpu().numpy()
-    return dict(lo=head[48:72].view(np.float64), inv_cs=head[72:96].view(np.float64),
-                dims=head[96:108].view(np.int32), ncells=int(head[108:112].view(np.uint32)[0]),
-                ntiles=int(head[112:116].view(np.uint32)[0]))
+    return pg.parse_grid_params(work[:128].cpu().numpy())
 
 
 def assert_planned(work, pos, reach, single, what):

@@ -8,6 +8,7 @@ import numpy as np
 import numpy.testing as npt
 import pytest
 
+from tests import pair_geometry as pg
 from tests import tpcf_oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -142,6 +143,41 @@ def test_grid_equals_single_cell(monkeypatch):
     single = gpu_counts(pos, 1000.0, s, MU40)
     npt.assert_array_equal(grid, single)
     assert grid.sum() > 10_000_000
+
+
+@pytest.mark.parametrize("case", list(pg.PERIODIC_CASES))
+def test_tpcf_plans_the_intended_grid(case, hip):
+    """ast_tpcf_prepare + ast_tpcf_pair_counts called directly: the GridBoxParams at the head of the workspace is the
+    periodic plan that tests/pair_geometry.py restates (dims, ncells, lo = 0, inv_cs = d / L bit for bit, ntiles), so
+    that a case which silently collapsed to one cell would be noticed, and the counts are the oracle's."""
+    from astrild_amd import _lib, device as dev
+    top, n, single, d = pg.PERIODIC_CASES[case]
+    box = pg.PERIODIC_L
+    pos = orc.uniform(n, box, 21)
+    s_edges, mu_edges = np.linspace(0.0, top, 6), np.array(LAT_MU)
+    ns, nmu = len(s_edges) - 1, len(mu_edges) - 1
+    p, s_d, mu_d = dev.as_device(pos), dev.as_device(s_edges), dev.as_device(mu_edges)
+    ws_bytes = hip.ast_tpcf_workspace_bytes(n, ns, nmu)
+    work = torch.empty(ws_bytes, dtype=torch.uint8, device="cuda")
+    bounds = torch.empty(6, dtype=torch.float64, device="cuda")
+    st = dev.stream()
+    _lib.check(hip.ast_tpcf_prepare(dev.ptr(p), _lib.F64, None, _lib.F64, 2, box, n, dev.ptr(work), ws_bytes,
+                                    dev.ptr(bounds), st), "ast_tpcf_prepare")
+    counts = torch.full((ns, nmu), -1, dtype=torch.int64, device="cuda")
+    _lib.check(hip.ast_tpcf_pair_counts(dev.ptr(work), ws_bytes, n, box, 2, dev.ptr(s_d), ns, dev.ptr(mu_d), nmu,
+                                        int(single), dev.ptr(counts), st), "ast_tpcf_pair_counts")
+    torch.cuda.synchronize()
+    got, want = pg.parse_grid_params(work[:128].cpu().numpy()), pg.plan_periodic(pos, box, top, single)
+    assert want.dims.tolist() == [d, d, d]
+    assert got["dims"].tolist() == [d, d, d]
+    assert got["ncells"] == d ** 3
+    assert got["ntiles"] == pg.tiles(want)
+    npt.assert_array_equal(got["lo"], np.zeros(3))
+    npt.assert_array_equal(got["inv_cs"], np.full(3, d / box if d > 1 else 0.0))
+    npt.assert_array_equal(got["inv_cs"], want.inv_cs)
+    ref = orc.pair_counts(pos, box, s_edges, mu_edges, los=2)
+    assert ref.sum() > 0
+    npt.assert_array_equal(counts.cpu().numpy(), ref)
 
 
 def test_counts_survive_lds_flushes(monkeypatch):

@@ -210,6 +210,22 @@ def test_a_planner_that_rounds_up_loses_pairs(name):
     assert np.all(lost >= 0) and lost.sum() >= 1 and lost[-1] >= 1     # the widest bin goes first
 
 
+@pytest.mark.parametrize("case", list(pg.PERIODIC_CASES))
+def test_the_periodic_plan_gives_the_stated_cells(case):
+    """The restatement of grid_periodic_plan alone: the cells per axis of the five cases, d / L bit for bit, every
+    object in a cell of the cube, and cells at least as wide as the reach."""
+    top, n, single, d = pg.PERIODIC_CASES[case]
+    pos = np.random.default_rng(11).uniform(0.0, pg.PERIODIC_L, (n, 3))
+    p = pg.plan_periodic(pos, pg.PERIODIC_L, top, single)
+    assert p.dims.tolist() == [d, d, d]
+    npt.assert_array_equal(p.lo, np.zeros(3))
+    npt.assert_array_equal(p.inv_cs, np.full(3, d / pg.PERIODIC_L if d > 1 else 0.0))
+    assert p.cell_id.min() >= 0 and p.cell_id.max() < d ** 3
+    assert d ** 3 <= max(27, n) and (d == 1 or (d >= 3 and pg.PERIODIC_L / d >= top))
+    # one cell: two tiles of its 300 objects; else fewer than a tile of objects in every cell
+    assert pg.tiles(p) == (-(-n // pg.TILE) if d == 1 else len(np.unique(p.cell_id)))
+
+
 # ------------------------------------------------------------------ the reference inside its own tolerance
 def sums_bound(cnt, sum_abs):
     """|a - b| of two orders of an fp64 sum of `cnt` terms: cnt 2^-52 sum|term|; at least 8 terms' worth, since the
