@@ -373,6 +373,57 @@ def add(a, b, out=None):
     return out
 
 
+# ------------------------------------------- Gaussian random maps from a C_l (create_cmb)
+def _grf_args(npix, cl, seed, realisation, nreal, lmax):
+    """The checked arguments of ast_grf_spectrum: (npix, host C_l table, seed, realisation, nreal, lmax)."""
+    npix, nreal = int(npix), int(nreal)
+    if npix < 2 or nreal < 1:
+        raise ValueError("gaussian random field: npix >= 2 and nreal >= 1 are expected")
+    cl = np.ascontiguousarray(cl, dtype=np.float64)
+    if cl.ndim != 1 or cl.size == 0:
+        raise ValueError("gaussian random field: the C_l table is one-dimensional and not empty")
+    if not np.isfinite(cl).all() or (cl < 0.0).any():
+        raise ValueError("gaussian random field: the C_l table holds a negative or non-finite value")
+    seed, realisation = int(seed), int(realisation)
+    if not 0 <= seed < 1 << 64 or not 0 <= realisation < 1 << 64:
+        raise ValueError("gaussian random field: seed and realisation lie in [0, 2^64)")
+    if realisation + nreal > 1 << 64:
+        raise ValueError("gaussian random field: realisation + nreal passes 2^64")
+    lmax = np.inf if lmax is None else float(lmax)
+    if np.isnan(lmax):
+        raise ValueError("gaussian random field: lmax is NaN")
+    return npix, cl, seed, realisation, nreal, lmax
+
+
+def gaussian_random_spectrum(npix, angle_deg, cl, seed, realisation=0, nreal=1, lmax=None):
+    """Half-plane spectra (nreal, npix, npix//2 + 1), complex128 on the device, of nreal Gaussian random npix x npix maps
+    of side angle_deg whose flat-sky power spectrum is ``cl`` (C at integer l = 0, 1, ..., linear in between, zero above
+    min(lmax, len(cl) - 1)): ``numpy.fft.irfft2`` of one of them is a map with flat_power_spectrum(map) ~ C_l.  A pure
+    function of (seed, realisation, pixel) - ast_grf_spectrum states it -, so realisation r of a batch is the single
+    call with ``realisation + r``."""
+    npix, cl, seed, realisation, nreal, lmax = _grf_args(npix, cl, seed, realisation, nreal, lmax)
+    table = as_device(cl)
+    spec = torch.empty((nreal, npix, npix // 2 + 1), dtype=torch.complex128, device=table.device)
+    check(_lib.lib().ast_grf_spectrum(ptr(spec), npix, float(np.deg2rad(angle_deg)), ptr(table), cl.size, lmax, seed,
+                                      realisation, nreal, stream()), "ast_grf_spectrum")
+    return spec
+
+
+def gaussian_random_map(npix, angle_deg, cl, seed, realisation=0, nreal=1, lmax=None, out=None):
+    """The maps of ``gaussian_random_spectrum``: float64 on the device, (npix, npix), or (nreal, npix, npix) for
+    nreal > 1.  The C2R transform may overwrite its input, so the spectrum is this function's own buffer."""
+    from . import device as dev
+    spec = gaussian_random_spectrum(npix, angle_deg, cl, seed, realisation, nreal, lmax)
+    nreal, npix = int(spec.shape[0]), int(spec.shape[1])
+    shape = (npix, npix) if nreal == 1 else (nreal, npix, npix)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float64, device=spec.device)
+    elif not (out.is_cuda and out.dtype == torch.float64 and tuple(out.shape) == shape and out.is_contiguous()):
+        raise ValueError(f"gaussian_random_map: out is a contiguous float64 CUDA tensor of shape {shape}")
+    dev.fft_plan(_lib.FFT_C2R, F64, (npix, npix), nreal, 1.0 / float(npix) ** 2, False).execute(spec, out)
+    return out
+
+
 # --------------------------------------------------- f-2 NFW halo stamps
 def nfw_stamp_npix(halo_cat, extent, stamp_npix=None):
     """Edge length [pixels] of every halo's stamp: ``int(2 * r200_pix * extent) + 1`` (sky_utils.py:112,130) unless the

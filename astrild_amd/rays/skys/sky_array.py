@@ -1,13 +1,10 @@
 """``SkyArray`` (src/astrild/rays/skys/sky_array.py) for the kappa-map hot path:
-unit conversion + reshape, PDF, filters, galaxy shape noise, kappa -> deflection,
-crop / division / merge.  ``self.data`` hands out numpy arrays like the reference's dict;
+unit conversion + reshape, PDF, filters, galaxy shape noise, CMB realisations, kappa ->
+deflection, crop / division / merge.  ``self.data`` hands out numpy arrays like the reference's dict;
 the arithmetic runs on the GPU through libastrild_hip.so, and what a method produces
 STAYS in HBM until somebody asks for the array (``rays/_resident.MapStore``): a chain
 filter -> kappa->alpha -> shear -> pdf makes one upload instead of a PCIe round trip
-per method (4096^2 float64: 134 MB each way, several times any of the kernels).
-
-Not carried over (out of scope): create_cmb (broken in the reference,
-sky_array.py:735-739)."""
+per method (4096^2 float64: 134 MB each way, several times any of the kernels)."""
 import copy
 from typing import Dict, List, Optional, Tuple, Union
 
@@ -270,6 +267,59 @@ class SkyArray:
             self.data["orig_gsn"] = lensing.add(self.data.device("orig"), self.data.device("gsn"))
             return self.data["orig_gsn"]
         raise SkyArrayWarning(f"GSN should not be added to {self.quantity}")
+
+    @staticmethod
+    def _load_cl_table(filepath_cl: str) -> np.ndarray:
+        """C_l at integer l = 0, 1, ... from a 2-row file (l, C_l^TT): row 1 as it is when row 0 is 0, 1, 2, ...; otherwise
+        ``np.interp`` onto l = 0 .. max l, zero outside the tabulated range."""
+        table = np.asarray(np.load(filepath_cl), dtype=np.float64)
+        if table.ndim != 2 or table.shape[0] < 2 or table.shape[1] < 1:
+            raise ValueError(f"{filepath_cl}: a 2-row array (l, C_l) is expected")
+        ell, cl = table[0], table[1]
+        if np.array_equal(ell, np.arange(len(ell))):
+            return cl
+        if not (np.isfinite(ell).all() and (np.diff(ell) > 0).all() and ell[-1] >= 0):
+            raise ValueError(f"{filepath_cl}: row 0 holds finite, ascending multipoles")
+        return np.interp(np.arange(int(np.floor(ell[-1])) + 1, dtype=np.float64), ell, cl, left=0.0, right=0.0)
+
+    def create_cmb(self, filepath_cl: str, lmax: int = 3e3, rnd_seed: Optional[int] = None,
+                   rtn: bool = False) -> Union[np.ndarray, None]:
+        """Primary-CMB realisation on the map's own grid (sky_array.py:709-739): a flat-sky Gaussian random field of
+        ``npix`` pixels and ``opening_angle`` degrees a side whose power spectrum is row 1 of the 2-row file
+        ``filepath_cl`` (l, C_l^TT) - ``lensing.gaussian_random_map``, stored as data["cmb"] in HBM or returned.
+        The reference's NaMaster ``synfast_flat`` call is commented out (it returns an undefined name); the generator
+        here is this project's own and not NaMaster's stream.  ``lmax`` is honoured, C_l = 0 above it (None: no cut); the
+        reference accepts it and drops it.  ``rnd_seed=None`` draws a 64-bit seed; the seed used is kept as
+        ``self.cmb_seed``."""
+        cl = self._load_cl_table(filepath_cl)
+        if rnd_seed is None:
+            rnd_seed = int(np.random.SeedSequence().entropy) & ((1 << 64) - 1)
+        self.cmb_seed = int(rnd_seed)
+        cmb = lensing.gaussian_random_map(self._npix, self._opening_angle, cl, self.cmb_seed, lmax=lmax)
+        if rtn:
+            return to_host(cmb)
+        self.data["cmb"] = cmb
+
+    def add_cmb(self, filepath_cl: Optional[str] = None, filepath_cmb: Optional[str] = None, on: str = "orig",
+                lmax: Optional[float] = None, rnd_seed: Optional[int] = None, rtn: bool = False,
+                overwrite: bool = True) -> Union[np.ndarray, None]:
+        """data[on] + data["cmb"] of an ISW / Rees-Sciama map (sky_array.py:742-777), summed on the device.  Without a
+        stored "cmb" it is made by ``create_cmb(filepath_cl, lmax, rnd_seed)`` (lmax None: no cut) or, with no
+        ``filepath_cl``, loaded from the .npy file ``filepath_cmb``.  The sum is returned, replaces data[on], or goes to
+        data[f"{on}_cmb"] (``overwrite=False``)."""
+        if "isw" not in self.quantity:
+            raise SkyArrayWarning(f"CMB should not be added to {self.quantity}")
+        if "cmb" not in self.data.keys():
+            if filepath_cl is not None:
+                self.create_cmb(filepath_cl, lmax, rnd_seed)
+            elif filepath_cmb is not None:
+                self.data["cmb"] = np.load(filepath_cmb)
+            else:
+                raise SkyArrayWarning("There is no CMB map: give filepath_cl or filepath_cmb")
+        _map = lensing.add(self.data.device(on), self.data.device("cmb"))
+        if rtn:
+            return to_host(_map)
+        self.data[on if overwrite else f"{on}_cmb"] = _map
 
     def convert_convergence_to_deflection(self, on: Optional[str] = None, img: Optional[np.ndarray] = None,
                                           npix: Optional[int] = None, opening_angle: Optional[float] = None,

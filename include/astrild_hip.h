@@ -708,6 +708,26 @@ int ast_flat_power_bin(const void* ft1_d, const void* ft2_d, int npix, double an
  * FFT estimator of the equilateral flat-sky bispectrum (bispectra/bispectrum_2d.py:33-50). */
 int ast_ring_filter_2d(const void* in_d, void* out_d, int npix, double angle_rad, double l_lo, double l_hi, void* stream);
 
+/* Gaussian random fields with a given flat-sky power spectrum (SkyArray.create_cmb / add_cmb,
+ * rays/skys/sky_array.py:709-777; the reference's NaMaster synfast_flat call is commented out, this is the project's own
+ * generator).  Fills nreal half-plane spectra, complex128, npix x (npix/2+1) row-major, one after the other in spec_d:
+ * the layout of the rfft2 above and of the C2R plan, whose numpy-convention inverse (1 / npix^2) is the map, with
+ * <|rfft2(map)|^2> (angle / npix^2)^2 = C(l), what ast_flat_power_bin measures.  Every slot is written; no scratch.
+ * Pixel (i, j) of realisation R = first_realisation + r, n = npix, nh = n/2 + 1, fp64 op by op:
+ *   l = (2 pi / angle) sqrt((double)(m^2 + j^2)), m = min(i, n - i);  cl_d[0 .. ncl-1] is C at integer l = 0 .. ncl-1;
+ *   k = floor(l), t = l - k, C = cl[k] + t (cl[min(k+1, ncl-1)] - cl[k]), C = 0 where l > min(lmax, ncl-1);
+ *   A = sqrt(C) s, s = (n n) / angle.
+ *   Columns j = 0 and (n even) j = n/2 are self-conjugate: there ic = min(i, (n-i) mod n), elsewhere ic = i.
+ *   (w0, w1, w2, w3) = Philox4x32-10(counter = (c lo, c hi, R lo, R hi), key = (seed lo, seed hi)), c = ic nh + j (64 bit);
+ *   u1 = (((w0 >> 5) 2^26 + (w1 >> 6)) + 1) 2^-53, u2 = ((w2 >> 5) 2^26 + (w3 >> 6)) 2^-53 (both exact);
+ *   r = sqrt(-2 log(u1)), phi = (2 pi) u2, a = r cos(phi), b = r sin(phi).
+ *   A self-conjugate pixel with i = (n-i) mod n gets (A a, 0); every other pixel ((A a) / sqrt(2), (A b) / sqrt(2)), the
+ *   imaginary part negated where i > (n-i) mod n in a self-conjugate column; A = 0 gives exactly (0, 0).
+ * The result is bit-identical from call to call and for any launch shape.  Refused before any launch: a null pointer,
+ * npix < 2, angle_rad not positive and finite, ncl < 1, nreal < 1, lmax NaN (+inf = no cut). */
+int ast_grf_spectrum(void* spec_d, int npix, double angle_rad, const double* cl_d, int ncl, double lmax,
+                     unsigned long long seed, unsigned long long first_realisation, int nreal, void* stream);
+
 /* Local maxima of an npix x npix map (SkyArray.wl_peak_counts, rays/skys/sky_array.py:435-472 ->
  * lenstools ConvergenceMap.locatePeaks): interior pixels strictly larger than their 8 neighbours with a
  * value in [lo, hi).  Heights go to values_d (dtype), flat row-major pixel indices to index_d, at most
