@@ -49,7 +49,7 @@ namespace ast {
 // (perfect-square |m|^2): those sit on an edge and the rounding of the float expressions decides between shell r - 1
 // and r - 2.  This restates that arithmetic for such a vector (no fma: the library is built with
 // -ffp-contract=off); kf = 0 selects the integer rule.  Returns floor(|m|) or floor(|m|) - 1.
-__device__ inline int float64_edge_norm(int r, int mx, int my, int mz, double kf) {
+__host__ __device__ inline int float64_edge_norm(int r, int mx, int my, int mz, double kf) {
     const double kx = kf * (double)mx, ky = kf * (double)my, kz = kf * (double)mz;
     const double k2 = (kx * kx + ky * ky) + kz * kz;
     const double e = kf + (double)(r - 1) * kf;

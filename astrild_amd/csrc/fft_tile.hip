@@ -134,7 +134,8 @@ __global__ void tile_isqrt_table_kernel(int* out, int count) {
 //   the z pass (rows_c2r_kernel) reads k_z < m_hi only.
 // A shell of radius N/4 moves 40 % of the full transform's bytes.
 struct ShellMask { const float2* src; long long lo2, hi2; int ky0 = 0; int pass = 0;       // ky0 (POWER): global k_y index of batch 0 (slab blocks)
-                   size_t src_elem_stride = 0, src_batch_stride = 0; };                    // strides of `src` when they differ from the destination's (0: the same)
+                   size_t src_elem_stride = 0, src_batch_stride = 0;                       // strides of `src` when they differ from the destination's (0: the same)
+                   int epi_skip = 0, no_nyq = 0; };        // POWER: the epilogue skips wave steps beyond the sphere / the tile of column N/2 counts as pruned (the k_y pass left it out)
 
 // PACK: the stores go to `pack.out` in the layout the slab transpose sends (what ast_slab_pack makes of the array): row
 // k_y of batch (plane) b lands in part k_y / c1 at ((part * nbatch + b) * c1 + k_y % c1) * pitch + column.
@@ -145,6 +146,9 @@ struct ShellMask { const float2* src; long long lo2, hi2; int ky0 = 0; int pass 
 constexpr int SHELL_BATCH = 8;
 #ifndef C2C_XCD_MODE
 #define C2C_XCD_MODE 2              // batch rows -> XCDs in strided_c2c_kernel: 0 never, 1 inverse passes, 2 all passes
+#endif
+#ifndef XPASS_ATOMICS
+#define XPASS_ATOMICS 1             // perf experiments on the binning epilogue's ds_add_f64 (scripts/perf_xpass_variants.py): 0 = none, 2 = lane-unique addresses
 #endif
 struct ShellBatch { int count = 0; float2* work[SHELL_BATCH]; long long lo2[SHELL_BATCH], hi2[SHELL_BATCH]; };
 struct C2RBatch { int count = 0; const float2* in[SHELL_BATCH]; float* out[SHELL_BATCH]; int kmax[SHELL_BATCH]; };
@@ -161,7 +165,7 @@ struct PackDst { float2* out = nullptr; unsigned c1_log2 = 0; unsigned nbatch = 
                  const DiscEntry* disc = nullptr; const unsigned short* gk = nullptr; unsigned part = 0;
                  unsigned xmajor = 0; };     // xmajor = N (one part only): element (x, row, col) of a tile at (row_pos * N + x) * 16 + col - the last pass reads N * 128 contiguous bytes
 
-template <int R1, int R2, int C, bool POWER, bool INV = false, int PACK = 0>
+template <int R1, int R2, int C, bool POWER, bool INV = false, int PACK = 0, bool TAB = false>      // TAB (POWER): one shell table per column lane
 __global__ void __launch_bounds__(C * (R1 > R2 ? R1 : R2))
 // N = 1024 with binning: 128 VGPRs, so that two 8-wave workgroups fit a CU (see SPLIT below)
 __attribute__((amdgpu_waves_per_eu((POWER || C > 16) && R1 * R2 >= 1024 ? 4 : 1, (POWER || C > 16) && R1 * R2 >= 1024 ? 4 : 8)))
@@ -234,9 +238,11 @@ strided_c2c_kernel(float2* __restrict__ data, const float2* __restrict__ tw_g, s
             disc_base = data + ((long long)e.offb + (long long)(subb * 16u));
             disc_S = e.S;
         }
-    } else if (!INV && POWER && mask.hi2 > 0) {
+    } else if (!INV && POWER && (mask.hi2 > 0 || mask.no_nyq)) {
         const long long kyi = (long long)b + mask.ky0, ky = kyi > N / 2 ? kyi - N : kyi;
-        if (ky * ky + (long long)(c0 * c0) > mask.hi2) {
+        // (no_nyq: of the tile that starts at column N/2 only the workgroup of k_y = 0 is not pruned anyway, and none of
+        // its modes - norm N/2 and up - is ever binned; the k_y pass has not transformed that column)
+        if ((mask.hi2 > 0 && ky * ky + (long long)(c0 * c0) > mask.hi2) || (mask.no_nyq && c0 >= (size_t)(N / 2))) {
             for (int i = threadIdx.x; i < NB; i += NT) partial[((size_t)b * tiles_per_batch + tile) * NB + i] = 0.0;
             return;
         }
@@ -346,6 +352,27 @@ strided_c2c_kernel(float2* __restrict__ data, const float2* __restrict__ tw_g, s
             }
         }
     }
+    // SHELL TABLES (TAB): a wave is 4 k_x by 16 adjacent k_z, and adjacent k_z mostly share a shell - 15.7 active lanes
+    // of a 16-lane group hit 8.3 distinct shells on average, 14 lanes one shell in tile 0 - so the ds_add_f64 of a wave
+    // queue up behind each other at one address: 0.16 of this pass's 0.98 ms at side 1024 (with every lane at an address of
+    // its own the pass takes what it takes with no atomics at all, scripts/perf_xpass_variants.py).  Once stage 2 has read
+    // the exchange buffer, it and the twiddles are dead: every column lane c gets a shell table of its own there, NB + 2
+    // doubles apart so that equal shells of different lanes lie in different banks; only the (at most 4) k_x of one lane can
+    // still meet.  The tables are added up in lane order below.
+    double* acc_tab = shell;
+    if (POWER && TAB) {
+        // (here, before the stage-2 transform: behind it a barrier would keep all of u[] alive at once, where the epilogue
+        // otherwise takes the outputs as they come - 88 bytes of scratch per lane at N = 1024)
+        __syncthreads();                              // every thread has its stage-2 inputs
+        double* const tab = reinterpret_cast<double*>(lds);
+        static_assert(!POWER || (size_t)C * (NB + 2) * sizeof(double) <= (size_t)(YN * C + N) * sizeof(float2), "shell tables fit the dead exchange buffer");
+        int tid_f = (int)threadIdx.x;
+        asm volatile("" : "+v"(tid_f));               // (nothing of this loop is to be formed at the top and carried here)
+#pragma unroll 1                                      // (one address register: u[] is live and the kernel has none to spare)
+        for (int i = tid_f; i < C * (NB + 2); i += NT) tab[i] = 0.0;
+        __syncthreads();
+        acc_tab = tab;
+    }
     if (sub < R1) {
         fft_reg<R2>(u);
         // (store addresses and the column test rebuilt from the thread id here: the 32-column variant is held to 128 VGPRs
@@ -414,7 +441,8 @@ strided_c2c_kernel(float2* __restrict__ data, const float2* __restrict__ tw_g, s
     asm volatile("" : "+v"(tid_e));                 // the epilogue's column comes from the thread id again: not carried (spilled) from the top
     if (POWER && (unsigned)c0 + (unsigned)(tid_e % C) < (unsigned)ncols && sub < R1) {
         // one ds_add_f64 per mode; merging a wave's equal-shell lanes first (ballot + cross-lane
-        // adds) measured slower: 16 kz x 4 kx lanes rarely share one shell
+        // adds) measured slower
+        if (TAB) acc_tab += (tid_e % C) * (NB + 2);
         // (the word is fetched HERE, not at the top: nothing of this epilogue may stay live across the two register
         // FFTs - the kernel is held to 128 VGPRs and every long-lived value there turned into scratch traffic)
         unsigned fallmask = 0;
@@ -423,9 +451,24 @@ strided_c2c_kernel(float2* __restrict__ data, const float2* __restrict__ tw_g, s
         const int kz = (int)c0 + tid_e % C;
         const int ky = kyi > N / 2 ? kyi - N : kyi;
         const int m2yz = ky * ky + kz * kz;
-        const float w = (kz > 0 && kz < N / 2) ? 2.0f : 1.0f;
+        // (TAB: a table belongs to one column, so its weight is applied once, where the tables are added up - a factor 2 is
+        // exact in either place - and the epilogue has a register for the table's offset)
+        const float w = TAB ? 1.0f : ((kz > 0 && kz < N / 2) ? 2.0f : 1.0f);
+        // WAVE SKIP (mask.epi_skip, with forward pruning): a wave holds 64 / C consecutive `sub` and the tile's columns from
+        // k_z0 up; when (its smallest |k_x| at this k2)^2 + k_y^2 + k_z0^2 > (N/2)^2 none of its modes reaches a shell - sh
+        // would come out above NB for every lane - and the whole step is left out on scalars, as the k_y pass's stores are.
+        // `>`, not `>=`: a vector of norm exactly N/2 may fall into the last shell.  A third of the (wave, k2) steps of the
+        // tiles the pruning keeps go this way (34 % of their modes lie beyond the sphere); the adds that remain keep their order.
+        const int wsub0 = __builtin_amdgcn_readfirstlane(tid_e) / C, wsub1 = wsub0 + 64 / C - 1;
+        const int kyw = __builtin_amdgcn_readfirstlane(ky);
+        const int room = (!INV && mask.epi_skip && mask.hi2 > 0) ? (int)mask.hi2 - kyw * kyw - (int)(c0 * c0) : 0x7fffffff;
+#if XPASS_ATOMICS == 0
+        double dead = 0.0;
+#endif
 #pragma unroll
         for (int k2 = 0; k2 < R2; ++k2) {
+            const int akx = R1 * k2 >= N / 2 ? N - (wsub1 + R1 * k2) : wsub0 + R1 * k2;      // smallest |k_x| in the wave
+            if (akx * akx > room) continue;
             const float2 x = u[bitrev(k2, ilog2(R2))];
             const int row = sub + R1 * k2;
             const int kx = row > N / 2 ? row - N : row;
@@ -434,13 +477,31 @@ strided_c2c_kernel(float2* __restrict__ data, const float2* __restrict__ tw_g, s
             sh -= (int)((fallmask >> k2) & 1u);
             // |delta_k|^2 in fp32 (one rounding of 6e-8 per mode, random over the >= 18 modes of a
             // shell), accumulated in double
-            if (sh >= 1 && sh <= NB) atomicAdd(&shell[sh], (double)(fmaf(x.x, x.x, x.y * x.y) * w));
+#if XPASS_ATOMICS == 1
+            if (sh >= 1 && sh <= NB) atomicAdd(&acc_tab[sh], (double)(fmaf(x.x, x.x, x.y * x.y) * w));
+#elif XPASS_ATOMICS == 2                                                  // every lane of a wave its own address (wrong sums)
+            if (sh >= 1 && sh <= NB) atomicAdd(&shell[(sh & (N / 2 - 64)) | (tid_e & 63)], (double)(fmaf(x.x, x.x, x.y * x.y) * w));
+#else                                                                     // no LDS atomics at all (wrong sums)
+            if (sh >= 1 && sh <= NB) dead += (double)(fmaf(x.x, x.x, x.y * x.y) * w);
+#endif
         }
+#if XPASS_ATOMICS == 0
+        if (dead == -1.0) shell[1] = dead;            // (never true: the sums are of squares; keeps the arithmetic alive)
+#endif
     }
     if (POWER) {
         __syncthreads();
         const double s2 = (double)scale * (double)scale;
-        for (int i = threadIdx.x; i < NB; i += NT) partial[((size_t)b * tiles_per_batch + tile) * NB + i] = shell[i + 1] * s2;
+        const double* const tab = TAB ? reinterpret_cast<const double*>(lds) : shell;
+        constexpr int copies = TAB ? C : 1;
+        int tid_w = (int)threadIdx.x;
+        if (TAB) asm volatile("" : "+v"(tid_w));
+        for (int i = tid_w; i < NB; i += NT) {
+            double t = tab[i + 1] * (TAB && c0 > 0 && c0 < (size_t)(N / 2) ? 2.0 : 1.0);     // (k_z = 0 and k_z = N/2: weight 1)
+            for (int cc = 1; cc < copies; ++cc)                                     // column lanes in order
+                t += tab[cc * (NB + 2) + i + 1] * ((int)c0 + cc < N / 2 ? 2.0 : 1.0);
+            partial[((size_t)b * tiles_per_batch + tile) * NB + i] = t * s2;
+        }
     }
 }
 
@@ -1340,7 +1401,7 @@ struct TwiddleCache {
 template <int R1, int R2, int C, bool POWER>
 int launch_c2c(float2* data, const float2* tw, size_t elem_stride, size_t ncols, size_t batch, size_t batch_stride,
                float scale, double* partial, hipStream_t s, const unsigned* edge_fall = nullptr, int ky0 = 0, long long prune2 = 0,
-               PackDst disc = PackDst{}) {
+               PackDst disc = PackDst{}, int epi_skip = 0, int no_nyq = 0, int tables = 0) {
     constexpr int N = R1 * R2, NT = C * (R1 > R2 ? R1 : R2);
     constexpr bool SPLIT = (POWER || C > 16) && R1 == R2 && N * C * sizeof(float2) > 64 * 1024;       // as in the kernel
     const size_t lds = (size_t)((SPLIT ? N / 2 : N) * C + N) * sizeof(float2) + (POWER ? (N / 2) * sizeof(double) : 0);
@@ -1348,14 +1409,24 @@ int launch_c2c(float2* data, const float2* tw, size_t elem_stride, size_t ncols,
     if (attr_once.need()) {
         AST_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&strided_c2c_kernel<R1, R2, C, POWER>),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        if (POWER) AST_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&strided_c2c_kernel<R1, R2, C, POWER, false, 0, POWER>),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         attr_once.mark();
     }
     const size_t tiles = (ncols + C - 1) / C;
     AST_CHECK_ARG(tiles * batch < 0x7fffffffull);
     AST_CHECK_ARG((size_t)(R2 - 1) * elem_stride + ncols < (1ull << 29));      // the kernel's 32-bit lane offsets
-    strided_c2c_kernel<R1, R2, C, POWER><<<(unsigned)(tiles * batch), NT, lds, s>>>(data, tw, elem_stride, ncols,
-                                                                                   batch_stride, (unsigned)tiles, scale,
-                                                                                   partial, edge_fall, ShellMask{nullptr, 0, prune2, ky0}, disc);
+    ShellMask mask{nullptr, 0, prune2, ky0};
+    mask.epi_skip = epi_skip;
+    mask.no_nyq = no_nyq;
+    if (POWER && tables)
+        strided_c2c_kernel<R1, R2, C, POWER, false, 0, POWER><<<(unsigned)(tiles * batch), NT, lds, s>>>(data, tw, elem_stride, ncols,
+                                                                                                       batch_stride, (unsigned)tiles, scale,
+                                                                                                       partial, edge_fall, mask, disc);
+    else
+        strided_c2c_kernel<R1, R2, C, POWER><<<(unsigned)(tiles * batch), NT, lds, s>>>(data, tw, elem_stride, ncols,
+                                                                                       batch_stride, (unsigned)tiles, scale,
+                                                                                       partial, edge_fall, mask, disc);
     AST_CHECK_LAUNCH();
     return AST_OK;
 }
@@ -1411,15 +1482,15 @@ int dispatch_c2c_inv(size_t n, float2* d, const float2* tw, size_t elem_stride, 
 template <bool POWER>
 int dispatch_c2c(size_t n, float2* d, const float2* tw, size_t elem_stride, size_t ncols, size_t batch,
                  size_t batch_stride, float scale, double* partial, hipStream_t s, const unsigned* edge_fall = nullptr, int ky0 = 0,
-                 long long prune2 = 0, PackDst disc = PackDst{}) {
+                 long long prune2 = 0, PackDst disc = PackDst{}, int epi_skip = 0, int no_nyq = 0, int tables = 0) {
 #ifndef FWD_C
 #define FWD_C 32                    // columns per workgroup of the plain forward pass at N = 1024: 32 = 256-byte row pieces, one 1024-thread
                                     // workgroup per CU with the split exchange (y pass 2.02 -> 1.91 ms); 16 = as in rounds 1-2
 #endif
     if constexpr (!POWER) { if (n == 1024) return launch_c2c<32, 32, FWD_C, false>(d, tw, elem_stride, ncols, batch, batch_stride, scale, partial, s, edge_fall, ky0, prune2); }
-    if (n == 1024) return launch_c2c<32, 32, 16, POWER>(d, tw, elem_stride, ncols, batch, batch_stride, scale, partial, s, edge_fall, ky0, prune2, disc);
-    if (n == 512) return launch_c2c<16, 32, 16, POWER>(d, tw, elem_stride, ncols, batch, batch_stride, scale, partial, s, edge_fall, ky0, prune2, disc);
-    return launch_c2c<16, 16, 16, POWER>(d, tw, elem_stride, ncols, batch, batch_stride, scale, partial, s, edge_fall, ky0, prune2, disc);
+    if (n == 1024) return launch_c2c<32, 32, 16, POWER>(d, tw, elem_stride, ncols, batch, batch_stride, scale, partial, s, edge_fall, ky0, prune2, disc, epi_skip, no_nyq, tables);
+    if (n == 512) return launch_c2c<16, 32, 16, POWER>(d, tw, elem_stride, ncols, batch, batch_stride, scale, partial, s, edge_fall, ky0, prune2, disc, epi_skip, no_nyq, tables);
+    return launch_c2c<16, 16, 16, POWER>(d, tw, elem_stride, ncols, batch, batch_stride, scale, partial, s, edge_fall, ky0, prune2, disc, epi_skip, no_nyq, tables);
 }
 
 template <int R1, int R2, int C, int FOLDW = 0, bool LOWK = false>
@@ -1850,7 +1921,7 @@ static int power_3d_impl(const void* grid, void* scratch, size_t scratch_bytes, 
     const double kf_rule = binning == AST_BIN_FLOAT64 ? 2.0 * M_PI / boxsize : 0.0;
     AST_CHECK_ARG(ast_fft_tile_supported(dtype, n));
     AST_CHECK_ARG(scratch_bytes >= ast_fft_tile_power_scratch_bytes(n));
-    const size_t nz = n / 2 + 1, nzp = (nz + 15) / 16 * 16, tiles = (nz + 15) / 16;
+    const size_t nz = n / 2 + 1, nzp = (nz + 15) / 16 * 16;
     float2* spec = (float2*)scratch;
     float2* disc = (float2*)((char*)scratch + n * n * nzp * sizeof(float2));
     double* partial = (double*)((char*)disc + power_disc_bytes(n));
@@ -1863,6 +1934,23 @@ static int power_3d_impl(const void* grid, void* scratch, size_t scratch_bytes, 
     double2* work = (double2*)((char*)modes + (LOWK_MODES * sizeof(double2) + 255) / 256 * 256);
     // the z pass forms the low-k z sums from the samples it holds anyway (AST_LOWK_SEPARATE: lowk_z_kernel instead)
     const bool z_fused = lowk && !getenv("AST_LOWK_SEPARATE");
+    // What the strided passes leave out besides the forward pruning (A/B switches restore the passes as they were):
+    //   the column k_z = n/2 (AST_FFT_NYQ_COLUMN=1: kept).  Of that whole plane only (0, 0, n/2) has |m| <= n/2, and its
+    //   norm is exactly n/2, one past the last shell's upper edge: the integer rule drops it, and so does the float64
+    //   rule at every side in use - for a power of two n/2 both kf * (n/2) and kf + (n/2 - 1) * kf come out as the same
+    //   double, so the comparison never lets it fall (tests/test_power_skip_cpu.py).  The rule is asked all the same, and
+    //   should it ever say "binned" the passes take the column as before.  Otherwise the k_y pass takes n/2 columns:
+    //   whole tiles only, 1/17 of its workgroups gone.  The last pass keeps its tiling (every workgroup of its last
+    //   tile but the one of k_y = 0 was pruned already; that one now is too), so column n/2 of the z pass's output is
+    //   never read.  (With n/2 columns and 32 tiles to a row the last pass lost 0.10 ms at side 1024 - see EXPERIMENTS.md.)
+    //   the epilogue steps of waves beyond the sphere (AST_FFT_NO_EPI_SKIP=1: done).
+    // And the last pass adds into one shell table per column lane (AST_FFT_SHELL_ATOMICS=1: into one table, as before).
+    // The disc-layout experiment below runs the passes as they were.
+    const char* disc_env = getenv("AST_FFT_DISC");
+    const bool disc_asked = !getenv("AST_FFT_NO_PRUNE") && disc_env != nullptr && (disc_env[0] == '1' || disc_env[0] == '2');
+    const bool nyq_binned = kf_rule != 0.0 && ast::float64_edge_norm((int)(n / 2), 0, 0, (int)(n / 2), kf_rule) != (int)(n / 2);
+    const bool no_nyq = !disc_asked && !nyq_binned && !getenv("AST_FFT_NYQ_COLUMN");
+    const size_t tiles = (nz + 15) / 16;
     auto lowk_rest = [&]() -> int {
         // the modes |m_i| <= MBOX as DFT sums in double, on the side stream, in their own part of the scratch
         AST_CHECK_HIP(hipEventRecord(side->in, s));                  // the grid (or the z sums) and the scratch are ready
@@ -1892,8 +1980,9 @@ static int power_3d_impl(const void* grid, void* scratch, size_t scratch_bytes, 
     const double inv_ng = 1.0 / ((double)n * (double)n * (double)n);
     // AST_FFT_DISC=1 (A/B runs): the k_y pass stores in the disc layout (one part) and the last pass reads it from there;
     // default: in place on the pitched rows, rows / tiles outside the disc skipped
-    const char* disc_env = getenv("AST_FFT_DISC");
-    const bool use_disc = prune2 != 0 && disc_env != nullptr && (disc_env[0] == '1' || disc_env[0] == '2');
+    const bool use_disc = disc_asked;
+    const int epi_skip = prune2 != 0 && !getenv("AST_FFT_NO_EPI_SKIP");
+    const int tables = !getenv("AST_FFT_SHELL_ATOMICS");
     const unsigned xmajor = use_disc && disc_env[0] == '2' ? (unsigned)n : 0u;      // 2: x-major tiles (experiment)
     if (use_disc) {
         const DiscLayout::Dev* dv = nullptr;
@@ -1928,7 +2017,7 @@ static int power_3d_impl(const void* grid, void* scratch, size_t scratch_bytes, 
     } else {
         {
             AST_PROF("fft_tile.c2c", s);
-            rc = dispatch_c2c<false>(n, spec, tw, nzp, nz, n, n * nzp, 1.0f, nullptr, s, nullptr, 0, prune2);       // y, per x-plane
+            rc = dispatch_c2c<false>(n, spec, tw, nzp, no_nyq ? n / 2 : nz, n, n * nzp, 1.0f, nullptr, s, nullptr, 0, prune2);       // y, per x-plane
             if (rc != AST_OK) return rc;
         }
         AST_PROF("fft_tile.c2c_power", s);
@@ -1937,7 +2026,7 @@ static int power_3d_impl(const void* grid, void* scratch, size_t scratch_bytes, 
             edge_fall = g_edge.get(n, boxsize, s);
             if (!edge_fall) { ast::set_error("ast_fft_tile_power_3d: edge table allocation failed"); return AST_ERR_HIP; }
         }
-        rc = dispatch_c2c<true>(n, spec, tw, n * nzp, nz, n, nzp, (float)inv_ng, partial, s, edge_fall, 0, prune2);   // x + binning
+        rc = dispatch_c2c<true>(n, spec, tw, n * nzp, nz, n, nzp, (float)inv_ng, partial, s, edge_fall, 0, prune2, PackDst{}, epi_skip, no_nyq, tables);   // x + binning
         if (rc != AST_OK) return rc;
     }
     AST_PROF("fft_tile.shell_reduce", s);
