@@ -5,6 +5,7 @@
 //   plan       grid_box_plan over a bounding box, grid_periodic_plan over a periodic cube, grid_plan choosing by boxsize;
 //   sort       grid_sort_set: clear, grid_box_count_kernel, grid_scan_kernel, grid_scatter_kernel;
 //   workspace  GridLayout, the one layout of a pair finder's scratch memory for one or two sets;
+//   host       grid_prepare, grid_sort_sets and GridSorted: a pair finder's entry points around its own kernels;
 //   walk       grid_pair_walk, the one walk of (tile of BLOCK objects of a cell, neighbour cell) work items by a
 //              persistent pair kernel, for one set or two, open or periodic;
 //   rows       grid_store_rows and grid_reduce3_kernel for kernels that sum (fp64, fp64, u64) per bin.
@@ -185,7 +186,7 @@ __device__ inline void grid_plan(GridBoxParams* prm, double reach, double boxsiz
     else grid_box_plan(prm, reach, cap, single);
 }
 
-// For a reach that the host knows (one whose reach lives in device memory has a plan kernel of its own).
+// For a reach that the host knows.
 // (Params is always GridBoxParams: a template only because a plain __global__ function is emitted into every file that
 // includes this header, launched or not.)
 template <typename Params>
@@ -193,6 +194,18 @@ __global__ void grid_box_plan_kernel(Params* prm, double rmax, unsigned cap, int
     static_assert(std::is_same<Params, GridBoxParams>::value, "grid_box_plan_kernel plans a GridBoxParams");
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     grid_box_plan(prm, rmax, cap, single);
+}
+
+// For a reach in device memory: the top edge, edges[nb], itself (pi_max <= 0), or sqrt(top^2 + pi_max^2) for pairs
+// within the top edge across and pi_max along a line of sight (grid_plan: periodic when boxsize > 0, else over the
+// bounding box).
+template <typename Params>
+__global__ void grid_edge_plan_kernel(Params* prm, const double* __restrict__ edges, int nb, double pi_max,
+                                      double boxsize, unsigned cap, int single) {
+    static_assert(std::is_same<Params, GridBoxParams>::value, "grid_edge_plan_kernel plans a GridBoxParams");
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const double top = edges[nb];
+    grid_plan(prm, pi_max > 0.0 ? sqrt(top * top + pi_max * pi_max) : top, boxsize, cap, single);
 }
 
 // ---- sort: objects ordered by cell with a counting sort
@@ -322,6 +335,59 @@ int grid_sort_set(char* ws, const GridLayout& L, int q, size_t n, hipStream_t s)
     AST_CHECK_LAUNCH();
     return AST_OK;
 }
+
+// ---- host: what the entry points of every pair finder do around their own prep and pair kernels
+// The counting sort and the walk index objects with 32 bits.
+inline bool grid_count_ok(size_t n) { return n < (size_t(1) << 31); }
+
+// No pair to visit: the outputs are zeroed and nothing is planned or sorted.
+inline bool grid_no_pairs(int auto_pairs, size_t n1, size_t n2) { return auto_pairs ? n1 < 2 : (n1 == 0 || n2 == 0); }
+
+// The prepare call of NSETS sets of n[q] objects, under the AST_PROF scope `prof`: per set the empty box and, when it
+// has objects, prep(q, obj, box), which launches the finder's prep kernel of set q into its records and its box.  Then
+// grid_bounds_kernel into bounds_d, for a caller that checks the coordinates; one that does not passes a literal
+// nullptr, and its file gets no bounds kernel.
+template <int NSETS, typename Obj, typename Bounds, typename Prep>
+int grid_prepare(char* ws, const GridLayout& L, const size_t* n, Bounds bounds_d, const char* prof, hipStream_t s,
+                 Prep&& prep) {
+    GridBounds* box[2] = {(GridBounds*)(ws + L.bounds[0]), (GridBounds*)(ws + L.bounds[NSETS - 1])};
+    {
+        AST_PROF(prof, s);
+        for (int q = 0; q < NSETS; ++q) {
+            if (int rc = grid_bounds_reset(box[q], s)) return rc;
+            if (n[q] == 0) continue;
+            prep(q, (Obj*)(ws + L.obj[q]), box[q]);
+            AST_CHECK_LAUNCH();
+        }
+    }
+    if constexpr (!std::is_same<Bounds, std::nullptr_t>::value) {
+        grid_bounds_kernel<NSETS><<<1, 64, 0, s>>>(box[0], box[1], &((GridBoxParams*)(ws + L.grid))->box, bounds_d);
+        AST_CHECK_LAUNCH();
+    }
+    return AST_OK;
+}
+
+// Sort sets q2 .. 0 of n[q] objects into the planned grid.  Set 1 (q = 0) last: its tile count stays in prm->ntiles.
+template <int BLOCK, typename Obj>
+int grid_sort_sets(char* ws, const GridLayout& L, int q2, const size_t* n, hipStream_t s) {
+    for (int q = q2; q >= 0; --q)
+        if (int rc = grid_sort_set<BLOCK, Obj>(ws, L, q, n[q], s)) return rc;
+    return AST_OK;
+}
+
+// What a pair kernel reads of a sorted workspace: the grid, set 1 with its tiles, set 2 = set q2 (0: set 1 itself, for
+// one set or the pairs within one), and the workgroup rows of Part.
+template <typename Obj, typename Part = double>
+struct GridSorted {
+    GridBoxParams* prm;
+    Part* part;
+    const Obj *sorted1, *sorted2;
+    const unsigned *cell_start1, *tile_start1, *cell_start2;
+    GridSorted(char* ws, const GridLayout& L, int q2)
+        : prm((GridBoxParams*)(ws + L.grid)), part((Part*)(ws + L.part)), sorted1((const Obj*)(ws + L.sorted[0])),
+          sorted2((const Obj*)(ws + L.sorted[q2])), cell_start1((const unsigned*)(ws + L.cell_start[0])),
+          tile_start1((const unsigned*)(ws + L.tile_start[0])), cell_start2((const unsigned*)(ws + L.cell_start[q2])) {}
+};
 
 // ---- walk
 // The cell whose tiles hold `tile`: tile_start[cell] <= tile < tile_start[cell + 1].

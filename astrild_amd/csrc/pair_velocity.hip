@@ -59,15 +59,6 @@ pb_prep_kernel(const TP* __restrict__ pos, const TV* __restrict__ vel, size_t n,
     grid_bounds_commit<256>(lo, hi, box);
 }
 
-// One thread: the shared grid for the reach of the kind: the top edge (radial), or sqrt(top^2 + pi_max^2) (los)
-// (grid_plan: periodic when boxsize > 0, else over the union bounding box).
-__global__ void pb_plan_kernel(GridBoxParams* prm, const double* __restrict__ edges, int nb, int kind, double pi_max,
-                               double boxsize, unsigned cap, int single) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const double top = edges[nb];
-    grid_plan(prm, kind == AST_PAIRVEL_LOS ? sqrt(top * top + pi_max * pi_max) : top, boxsize, cap, single);
-}
-
 __device__ inline double pb_pick(const double* r, int k) { return k == 0 ? r[0] : (k == 1 ? r[1] : r[2]); }
 
 // The signed separation of one axis: with a period, the image within half a box.  Exactly antisymmetric under i <-> j,
@@ -181,19 +172,6 @@ pb_pair_kernel(const PbObj* __restrict__ sorted1, const unsigned* __restrict__ c
     grid_store_rows<PB_WAVES, PB_GRID>(h1, h2, hc, nb, part);
 }
 
-// Prep of one set; its box must have been reset.
-int pb_prep(const void* pos, int pos_dtype, const void* vel, int vel_dtype, size_t n, PbObj* obj, GridBounds* box,
-            hipStream_t s) {
-    if (n == 0) return AST_OK;
-    ast::dispatch_f32_f64(pos_dtype == AST_F32, vel_dtype == AST_F32, [&](auto tp, auto tv) {
-        using TP = decltype(tp);
-        using TV = decltype(tv);
-        pb_prep_kernel<TP, TV><<<ast::stream_grid(n, 256), 256, 0, s>>>((const TP*)pos, (const TV*)vel, n, obj, box);
-    });
-    AST_CHECK_LAUNCH();
-    return AST_OK;
-}
-
 }  // namespace
 
 extern "C" size_t ast_pairvel_workspace_bytes(size_t n1, size_t n2, int nb) {
@@ -210,29 +188,25 @@ extern "C" int ast_pairvel_prepare(const void* pos1_d, int pos1_dtype, const voi
                               (vel1_dtype == AST_F32 || vel1_dtype == AST_F64)));
     AST_CHECK_ARG(n2 == 0 || ((pos2_dtype == AST_F32 || pos2_dtype == AST_F64) &&
                               (vel2_dtype == AST_F32 || vel2_dtype == AST_F64)));
-    AST_CHECK_ARG(n1 < (size_t(1) << 31) && n2 < (size_t(1) << 31));
+    AST_CHECK_ARG(grid_count_ok(n1) && grid_count_ok(n2));
     AST_CHECK_ARG((n1 == 0 || (pos1_d && vel1_d)) && (n2 == 0 || (pos2_d && vel2_d)));
     AST_CHECK_ARG(bounds_d);
     const GridLayout L = pb_layout(n1, n2, 1);
     AST_CHECK_ARG(work_d && work_bytes >= L.part);
     hipStream_t s = ast::as_stream(stream);
-    char* ws = (char*)work_d;
-    GridBounds* box[2] = {(GridBounds*)(ws + L.bounds[0]), (GridBounds*)(ws + L.bounds[1])};
     const void* pos[2] = {pos1_d, pos2_d};
     const void* vel[2] = {vel1_d, vel2_d};
     const int pos_dtype[2] = {pos1_dtype, pos2_dtype}, vel_dtype[2] = {vel1_dtype, vel2_dtype};
     const size_t n[2] = {n1, n2};
-    {
-        AST_PROF("pairvel_prep", s);
-        for (int q = 0; q < 2; ++q) {
-            if (int rc = grid_bounds_reset(box[q], s)) return rc;
-            if (int rc = pb_prep(pos[q], pos_dtype[q], vel[q], vel_dtype[q], n[q], (PbObj*)(ws + L.obj[q]), box[q], s))
-                return rc;
-        }
-    }
-    grid_bounds_kernel<2><<<1, 64, 0, s>>>(box[0], box[1], &((GridBoxParams*)(ws + L.grid))->box, bounds_d);
-    AST_CHECK_LAUNCH();
-    return AST_OK;
+    return grid_prepare<2, PbObj>((char*)work_d, L, n, bounds_d, "pairvel_prep", s,
+                                  [&](int q, PbObj* obj, GridBounds* box) {
+        ast::dispatch_f32_f64(pos_dtype[q] == AST_F32, vel_dtype[q] == AST_F32, [&](auto tp, auto tv) {
+            using TP = decltype(tp);
+            using TV = decltype(tv);
+            pb_prep_kernel<TP, TV><<<ast::stream_grid(n[q], 256), 256, 0, s>>>((const TP*)pos[q], (const TV*)vel[q],
+                                                                                 n[q], obj, box);
+        });
+    });
 }
 
 extern "C" int ast_pairvel_moments(void* work_d, size_t work_bytes, size_t n1, size_t n2, int auto_pairs,
@@ -244,11 +218,11 @@ extern "C" int ast_pairvel_moments(void* work_d, size_t work_bytes, size_t n1, s
     AST_CHECK_ARG(los >= 0 && los <= 2);
     AST_CHECK_ARG(kind == AST_PAIRVEL_RADIAL || (pi_max > 0.0 && std::isfinite(pi_max)));
     AST_CHECK_ARG(boxsize >= 0.0 && std::isfinite(boxsize));
-    AST_CHECK_ARG(n1 < (size_t(1) << 31) && n2 < (size_t(1) << 31));
+    AST_CHECK_ARG(grid_count_ok(n1) && grid_count_ok(n2));
     AST_CHECK_ARG(edges_d && count_d && s1_d && s2_d);
     AST_CHECK_ARG(work_d && work_bytes >= ast_pairvel_workspace_bytes(n1, n2, nb));
     hipStream_t s = ast::as_stream(stream);
-    if (auto_pairs ? n1 < 2 : (n1 == 0 || n2 == 0)) {
+    if (grid_no_pairs(auto_pairs, n1, n2)) {
         AST_CHECK_HIP(hipMemsetAsync(count_d, 0, nb * sizeof(unsigned long long), s));
         AST_CHECK_HIP(hipMemsetAsync(s1_d, 0, nb * sizeof(double), s));
         AST_CHECK_HIP(hipMemsetAsync(s2_d, 0, nb * sizeof(double), s));
@@ -256,39 +230,28 @@ extern "C" int ast_pairvel_moments(void* work_d, size_t work_bytes, size_t n1, s
     }
     const GridLayout L = pb_layout(n1, n2, nb);
     char* ws = (char*)work_d;
-    GridBoxParams* prm = (GridBoxParams*)(ws + L.grid);
-    double* part = (double*)(ws + L.part);
     const size_t n[2] = {n1, n2};
     const int q2 = auto_pairs ? 0 : 1;
-    if (kind == AST_PAIRVEL_RADIAL) pi_max = 0.0;
+    const GridSorted<PbObj> g(ws, L, q2);
+    if (kind == AST_PAIRVEL_RADIAL) pi_max = 0.0;       // the reach is the top edge itself
     {
         AST_PROF("pairvel_grid", s);
-        pb_plan_kernel<<<1, 64, 0, s>>>(prm, edges_d, nb, kind, pi_max, boxsize, (unsigned)L.cap, single_cell);
+        grid_edge_plan_kernel<<<1, 64, 0, s>>>(g.prm, edges_d, nb, pi_max, boxsize, (unsigned)L.cap, single_cell);
         AST_CHECK_LAUNCH();
-        for (int q = q2; q >= 0; --q)               // set 1 last: its tile count stays in prm->ntiles
-            if (int rc = grid_sort_set<PB_BLOCK, PbObj>(ws, L, q, n[q], s)) return rc;
+        if (int rc = grid_sort_sets<PB_BLOCK, PbObj>(ws, L, q2, n, s)) return rc;
     }
     const size_t lds = pb_lds_bytes(nb);
     AST_CHECK_ARG(lds <= PB_LDS);
-    const PbObj* sorted1 = (const PbObj*)(ws + L.sorted[0]);
-    const PbObj* sorted2 = (const PbObj*)(ws + L.sorted[q2]);
-    const unsigned* cs1 = (const unsigned*)(ws + L.cell_start[0]);
-    const unsigned* cs2 = (const unsigned*)(ws + L.cell_start[q2]);
-    const unsigned* ts1 = (const unsigned*)(ws + L.tile_start[0]);
     {
         AST_PROF("pairvel_pairs", s);
-        if (kind == AST_PAIRVEL_LOS)
-            pb_pair_kernel<AST_PAIRVEL_LOS><<<PB_GRID, PB_BLOCK, lds, s>>>(sorted1, cs1, ts1, sorted2, cs2, prm, boxsize,
-                                                                           auto_pairs, los, pi_max, edges_d, nb, part);
-        else
-            pb_pair_kernel<AST_PAIRVEL_RADIAL><<<PB_GRID, PB_BLOCK, lds, s>>>(sorted1, cs1, ts1, sorted2, cs2, prm,
-                                                                              boxsize, auto_pairs, los, pi_max, edges_d,
-                                                                              nb, part);
+        const auto pairs = kind == AST_PAIRVEL_LOS ? pb_pair_kernel<AST_PAIRVEL_LOS> : pb_pair_kernel<AST_PAIRVEL_RADIAL>;
+        pairs<<<PB_GRID, PB_BLOCK, lds, s>>>(g.sorted1, g.cell_start1, g.tile_start1, g.sorted2, g.cell_start2, g.prm,
+                                             boxsize, auto_pairs, los, pi_max, edges_d, nb, g.part);
         AST_CHECK_LAUNCH();
     }
     {
         AST_PROF("pairvel_reduce", s);
-        grid_reduce3_kernel<PB_GRID><<<(nb + 255) / 256, 256, 0, s>>>(part, nb, s1_d, s2_d, count_d);
+        grid_reduce3_kernel<PB_GRID><<<(nb + 255) / 256, 256, 0, s>>>(g.part, nb, s1_d, s2_d, count_d);
         AST_CHECK_LAUNCH();
     }
     return AST_OK;

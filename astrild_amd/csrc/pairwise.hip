@@ -135,36 +135,31 @@ extern "C" int ast_pairwise_tv_prepare(const void* pos_d, int pos_dtype, const v
     AST_CHECK_ARG(vel_ncomp == 2 || vel_ncomp == 3);
     AST_CHECK_ARG(angle_mode >= 0 && angle_mode <= 2);
     AST_CHECK_ARG(angle_mode == 0 || vel_ncomp == 3 || n == 0 || (theta1_d && theta2_d));
-    AST_CHECK_ARG(n < (size_t(1) << 31));
+    AST_CHECK_ARG(grid_count_ok(n));
     AST_CHECK_ARG(n == 0 || (pos_d && vel_d));
     const GridLayout L = pv_layout(n, 1);
     AST_CHECK_ARG(work_d && work_bytes >= L.sorted[0]);
     hipStream_t s = ast::as_stream(stream);
-    char* ws = (char*)work_d;
-    GridBounds* box = (GridBounds*)(ws + L.bounds[0]);
-    if (int rc = grid_bounds_reset(box, s)) return rc;
-    if (n == 0) return AST_OK;
-    AST_PROF("pairwise_prep", s);
-    PvObj* obj = (PvObj*)(ws + L.obj[0]);
-    ast::dispatch_f32_f64(pos_dtype == AST_F32, vel_dtype == AST_F32, [&](auto tp, auto tv) {
-        using TP = decltype(tp);
-        using TV = decltype(tv);
-        pv_prep_kernel<TP, TV><<<ast::stream_grid(n, 256), 256, 0, s>>>(
-            (const TP*)pos_d, (const TV*)vel_d, vel_ncomp, theta1_d, theta2_d, angle_mode, n, obj, box);
+    return grid_prepare<1, PvObj>((char*)work_d, L, &n, nullptr, "pairwise_prep", s,
+                                  [&](int, PvObj* obj, GridBounds* box) {
+        ast::dispatch_f32_f64(pos_dtype == AST_F32, vel_dtype == AST_F32, [&](auto tp, auto tv) {
+            using TP = decltype(tp);
+            using TV = decltype(tv);
+            pv_prep_kernel<TP, TV><<<ast::stream_grid(n, 256), 256, 0, s>>>(
+                (const TP*)pos_d, (const TV*)vel_d, vel_ncomp, theta1_d, theta2_d, angle_mode, n, obj, box);
+        });
     });
-    AST_CHECK_LAUNCH();
-    return AST_OK;
 }
 
 extern "C" int ast_pairwise_tv(void* work_d, size_t work_bytes, size_t n, int binnr, double binwidth, int single_cell,
                                double* nom_d, double* denom_d, unsigned long long* counts_d, void* stream) {
     AST_CHECK_ARG(binnr >= 1 && binnr <= PV_MAX_BINS);
     AST_CHECK_ARG(binwidth > 0.0 && std::isfinite(binwidth));
-    AST_CHECK_ARG(n < (size_t(1) << 31));
+    AST_CHECK_ARG(grid_count_ok(n));
     AST_CHECK_ARG(nom_d && denom_d && counts_d);
     AST_CHECK_ARG(work_d && work_bytes >= ast_pairwise_workspace_bytes(n, binnr));
     hipStream_t s = ast::as_stream(stream);
-    if (n < 2) {
+    if (grid_no_pairs(1, n, 0)) {
         AST_CHECK_HIP(hipMemsetAsync(nom_d, 0, binnr * sizeof(double), s));
         AST_CHECK_HIP(hipMemsetAsync(denom_d, 0, binnr * sizeof(double), s));
         AST_CHECK_HIP(hipMemsetAsync(counts_d, 0, binnr * sizeof(unsigned long long), s));
@@ -172,17 +167,13 @@ extern "C" int ast_pairwise_tv(void* work_d, size_t work_bytes, size_t n, int bi
     }
     const GridLayout L = pv_layout(n, binnr);
     char* ws = (char*)work_d;
-    GridBoxParams* prm = (GridBoxParams*)(ws + L.grid);
-    const unsigned* cell_start = (const unsigned*)(ws + L.cell_start[0]);
-    const unsigned* tile_start = (const unsigned*)(ws + L.tile_start[0]);
-    const PvObj* sorted = (const PvObj*)(ws + L.sorted[0]);
-    double* part = (double*)(ws + L.part);
+    const GridSorted<PvObj> g(ws, L, 0);
     const double rmax = (double)binnr * binwidth;
     {
         AST_PROF("pairwise_grid", s);
-        grid_box_plan_kernel<<<1, 64, 0, s>>>(prm, rmax, (unsigned)L.cap, single_cell);
+        grid_box_plan_kernel<<<1, 64, 0, s>>>(g.prm, rmax, (unsigned)L.cap, single_cell);
         AST_CHECK_LAUNCH();
-        if (int rc = grid_sort_set<PV_BLOCK, PvObj>(ws, L, 0, n, s)) return rc;
+        if (int rc = grid_sort_sets<PV_BLOCK, PvObj>(ws, L, 0, &n, s)) return rc;
     }
     // Pre-test on d^2 with a relative margin far above the rounding of d and d / binwidth: every pair whose
     // int(d / binwidth) < binnr passes it; the bin decision itself is the fp64 int(d / binwidth) < binnr.
@@ -190,12 +181,13 @@ extern "C" int ast_pairwise_tv(void* work_d, size_t work_bytes, size_t n, int bi
     const size_t lds = (size_t)9 * PV_BLOCK * sizeof(double) + (size_t)PV_WAVES * binnr * 24;
     {
         AST_PROF("pairwise_pairs", s);
-        pv_pair_kernel<<<PV_GRID, PV_BLOCK, lds, s>>>(sorted, cell_start, tile_start, prm, binnr, binwidth, reach2, part);
+        pv_pair_kernel<<<PV_GRID, PV_BLOCK, lds, s>>>(g.sorted1, g.cell_start1, g.tile_start1, g.prm, binnr, binwidth,
+                                                      reach2, g.part);
         AST_CHECK_LAUNCH();
     }
     {
         AST_PROF("pairwise_reduce", s);
-        grid_reduce3_kernel<PV_GRID><<<(binnr + 255) / 256, 256, 0, s>>>(part, binnr, nom_d, denom_d, counts_d);
+        grid_reduce3_kernel<PV_GRID><<<(binnr + 255) / 256, 256, 0, s>>>(g.part, binnr, nom_d, denom_d, counts_d);
         AST_CHECK_LAUNCH();
     }
     return AST_OK;

@@ -202,24 +202,20 @@ extern "C" int ast_pairwise_pdf_prepare(const void* pos_d, int pos_dtype, const 
                                         void* work_d, size_t work_bytes, void* stream) {
     AST_CHECK_ARG(pos_dtype == AST_F32 || pos_dtype == AST_F64);
     AST_CHECK_ARG(vel_dtype == AST_F32 || vel_dtype == AST_F64);
-    AST_CHECK_ARG(n < (size_t(1) << 31));
+    AST_CHECK_ARG(grid_count_ok(n));
     AST_CHECK_ARG(n == 0 || (pos_d && vel_d));
     const GridLayout L = pd_layout(n, 0);
     AST_CHECK_ARG(work_d && work_bytes >= L.sorted[0]);
     hipStream_t s = ast::as_stream(stream);
-    char* ws = (char*)work_d;
-    GridBounds* box = (GridBounds*)(ws + L.bounds[0]);
-    if (int rc = grid_bounds_reset(box, s)) return rc;
-    if (n == 0) return AST_OK;
-    AST_PROF("pairwise_pdf_prep", s);
-    PdObj* obj = (PdObj*)(ws + L.obj[0]);
-    ast::dispatch_f32_f64(pos_dtype == AST_F32, vel_dtype == AST_F32, [&](auto tp, auto tv) {
-        using TP = decltype(tp);
-        using TV = decltype(tv);
-        pd_prep_kernel<TP, TV><<<ast::stream_grid(n, 256), 256, 0, s>>>((const TP*)pos_d, (const TV*)vel_d, n, obj, box);
+    return grid_prepare<1, PdObj>((char*)work_d, L, &n, nullptr, "pairwise_pdf_prep", s,
+                                  [&](int, PdObj* obj, GridBounds* box) {
+        ast::dispatch_f32_f64(pos_dtype == AST_F32, vel_dtype == AST_F32, [&](auto tp, auto tv) {
+            using TP = decltype(tp);
+            using TV = decltype(tv);
+            pd_prep_kernel<TP, TV><<<ast::stream_grid(n, 256), 256, 0, s>>>((const TP*)pos_d, (const TV*)vel_d, n, obj,
+                                                                             box);
+        });
     });
-    AST_CHECK_LAUNCH();
-    return AST_OK;
 }
 
 extern "C" int ast_pairwise_pdf(void* work_d, size_t work_bytes, size_t n, int kind, double r, int dist_bin,
@@ -235,7 +231,7 @@ extern "C" int ast_pairwise_pdf(void* work_d, size_t work_bytes, size_t n, int k
     AST_CHECK_ARG(reach > 0.0 && std::isfinite(reach));
     AST_CHECK_ARG(dist_width > 0.0 && std::isfinite(dist_width));
     AST_CHECK_ARG(vel_width > 0.0 && std::isfinite(vel_width));
-    AST_CHECK_ARG(n < (size_t(1) << 31));
+    AST_CHECK_ARG(grid_count_ok(n));
     AST_CHECK_ARG(first <= second && second <= n);
     AST_CHECK_ARG(hist_d && outside_d);
     AST_CHECK_ARG(work_d && work_bytes >= ast_pairwise_pdf_workspace_bytes(n, dist_bin, vel_bin, moments));
@@ -243,7 +239,7 @@ extern "C" int ast_pairwise_pdf(void* work_d, size_t work_bytes, size_t n, int k
     const int nbins = dist_bin * vel_bin;
     AST_CHECK_HIP(hipMemsetAsync(hist_d, 0, (size_t)nbins * sizeof(unsigned long long), s));
     AST_CHECK_HIP(hipMemsetAsync(outside_d, 0, sizeof(unsigned long long), s));
-    if (n < 2 || first == second) {
+    if (grid_no_pairs(1, n, 0) || first == second) {
         if (moments) {
             AST_CHECK_HIP(hipMemsetAsync(s1_d, 0, dist_bin * sizeof(double), s));
             AST_CHECK_HIP(hipMemsetAsync(s2_d, 0, dist_bin * sizeof(double), s));
@@ -253,16 +249,12 @@ extern "C" int ast_pairwise_pdf(void* work_d, size_t work_bytes, size_t n, int k
     }
     const GridLayout L = pd_layout(n, moments ? dist_bin : 0);
     char* ws = (char*)work_d;
-    GridBoxParams* prm = (GridBoxParams*)(ws + L.grid);
-    const unsigned* cell_start = (const unsigned*)(ws + L.cell_start[0]);
-    const unsigned* tile_start = (const unsigned*)(ws + L.tile_start[0]);
-    const PdObj* sorted = (const PdObj*)(ws + L.sorted[0]);
-    double* part = (double*)(ws + L.part);
+    const GridSorted<PdObj> g(ws, L, 0);
     {
         AST_PROF("pairwise_pdf_grid", s);
-        grid_box_plan_kernel<<<1, 64, 0, s>>>(prm, reach, (unsigned)L.cap, single_cell);
+        grid_box_plan_kernel<<<1, 64, 0, s>>>(g.prm, reach, (unsigned)L.cap, single_cell);
         AST_CHECK_LAUNCH();
-        if (int rc = grid_sort_set<PD_BLOCK, PdObj>(ws, L, 0, n, s)) return rc;
+        if (int rc = grid_sort_sets<PD_BLOCK, PdObj>(ws, L, 0, &n, s)) return rc;
     }
     PdBins bn;
     bn.kind = kind;
@@ -296,17 +288,14 @@ extern "C" int ast_pairwise_pdf(void* work_d, size_t work_bytes, size_t n, int k
     }
     {
         AST_PROF(use_lds ? "pairwise_pdf_pairs_lds" : "pairwise_pdf_pairs_global", s);
-        if (use_lds)
-            pd_pair_kernel<true><<<PD_GRID, PD_BLOCK, lds, s>>>(sorted, cell_start, tile_start, prm, bn, flush_at, hist_d,
-                                                                outside_d, part);
-        else
-            pd_pair_kernel<false><<<PD_GRID, PD_BLOCK, lds, s>>>(sorted, cell_start, tile_start, prm, bn, flush_at,
-                                                                 hist_d, outside_d, part);
+        const auto pairs = use_lds ? pd_pair_kernel<true> : pd_pair_kernel<false>;
+        pairs<<<PD_GRID, PD_BLOCK, lds, s>>>(g.sorted1, g.cell_start1, g.tile_start1, g.prm, bn, flush_at, hist_d,
+                                             outside_d, g.part);
         AST_CHECK_LAUNCH();
     }
     if (moments) {
         AST_PROF("pairwise_pdf_reduce", s);
-        grid_reduce3_kernel<PD_GRID><<<(dist_bin + 255) / 256, 256, 0, s>>>(part, dist_bin, s1_d, s2_d, mcount_d);
+        grid_reduce3_kernel<PD_GRID><<<(dist_bin + 255) / 256, 256, 0, s>>>(g.part, dist_bin, s1_d, s2_d, mcount_d);
         AST_CHECK_LAUNCH();
     }
     return AST_OK;

@@ -70,13 +70,6 @@ tp_prep_kernel(const TP* __restrict__ pos, const TV* __restrict__ vel, int los, 
     grid_bounds_commit<256>(lo, hi, box);
 }
 
-// One thread: the grid for a reach of the top s edge (grid_plan: periodic when boxsize > 0, else over the bounding box).
-__global__ void tp_plan_kernel(GridBoxParams* prm, const double* __restrict__ s_edges, int ns, double boxsize,
-                               unsigned cap, int single) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    grid_plan(prm, s_edges[ns], boxsize, cap, single);
-}
-
 // What a pair kernel needs beside the grid: the box, the edges in device memory, and tp_bins' choices.
 struct TpBins {
     double boxsize;
@@ -207,18 +200,15 @@ tp_reduce_kernel(const unsigned long long* __restrict__ part, int nbins, unsigne
     counts[bin] = sum;
 }
 
-// Prep of one set; its box must have been reset.
-int tp_prep(const void* pos, int pos_dtype, const void* vel, int vel_dtype, int los, double boxsize, size_t n,
-            TpObj* obj, GridBounds* box, hipStream_t s) {
-    if (n == 0) return AST_OK;
+// The launch of the prep kernel of one non-empty set.
+void tp_prep(const void* pos, int pos_dtype, const void* vel, int vel_dtype, int los, double boxsize, size_t n,
+             TpObj* obj, GridBounds* box, hipStream_t s) {
     ast::dispatch_f32_f64(pos_dtype == AST_F32, vel && vel_dtype == AST_F32, [&](auto tp, auto tv) {
         using TP = decltype(tp);
         using TV = decltype(tv);
         tp_prep_kernel<TP, TV><<<ast::stream_grid(n, 256), 256, 0, s>>>((const TP*)pos, (const TV*)vel, los, boxsize, n,
                                                                          obj, box);
     });
-    AST_CHECK_LAUNCH();
-    return AST_OK;
 }
 
 // The bins of a call and the dynamic LDS of its pair kernel.  Histogram copies: one per wave where the LDS budget
@@ -234,6 +224,40 @@ TpBins tp_bins(double boxsize, int los, const double* s_edges, int ns, const dou
     if (const char* f = getenv("AST_TPCF_FLUSH_AT")) flush_at = strtoull(f, nullptr, 10);
     if (flush_at > TP_FLUSH_AT) flush_at = TP_FLUSH_AT;
     return TpBins{boxsize, los, s_edges, ns, mu_edges, nmu, hcopies, flush_at};
+}
+
+// The pair counts of a prepared workspace with pairs in it: the plan for the top s edge, the sort, the pair kernel -
+// tp_pair_kernel for the one set of ast_tpcf_* (`cross` false), else tpx_pair_kernel - and the reduce.
+int tp_counts(bool cross, char* ws, const GridLayout& L, const size_t* n, int auto_pairs, double boxsize, int los,
+              const double* s_edges_d, int ns, const double* mu_edges_d, int nmu, int single_cell,
+              unsigned long long* counts_d, hipStream_t s) {
+    const int nbins = nbins_of(ns, nmu);
+    const int q2 = cross && !auto_pairs ? 1 : 0;
+    const GridSorted<TpObj, unsigned long long> g(ws, L, q2);
+    {
+        AST_PROF(cross ? "tpcf_cross_grid" : "tpcf_grid", s);
+        grid_edge_plan_kernel<<<1, 64, 0, s>>>(g.prm, s_edges_d, ns, 0.0, boxsize, (unsigned)L.cap, single_cell);
+        AST_CHECK_LAUNCH();
+        if (int rc = grid_sort_sets<TP_BLOCK, TpObj>(ws, L, q2, n, s)) return rc;
+    }
+    size_t lds;
+    const TpBins bn = tp_bins(boxsize, los, s_edges_d, ns, mu_edges_d, nmu, &lds);
+    AST_CHECK_ARG(lds <= TP_LDS);
+    {
+        AST_PROF(cross ? "tpcf_cross_pairs" : "tpcf_pairs", s);
+        if (cross)
+            tpx_pair_kernel<<<TP_GRID, TP_BLOCK, lds, s>>>(g.sorted1, g.cell_start1, g.tile_start1, g.sorted2,
+                                                           g.cell_start2, g.prm, auto_pairs, bn, g.part);
+        else
+            tp_pair_kernel<<<TP_GRID, TP_BLOCK, lds, s>>>(g.sorted1, g.cell_start1, g.tile_start1, g.prm, bn, g.part);
+        AST_CHECK_LAUNCH();
+    }
+    {
+        AST_PROF(cross ? "tpcf_cross_reduce" : "tpcf_reduce", s);
+        tp_reduce_kernel<<<(nbins + 255) / 256, 256, 0, s>>>(g.part, nbins, counts_d);
+        AST_CHECK_LAUNCH();
+    }
+    return AST_OK;
 }
 
 }  // namespace
@@ -252,23 +276,15 @@ extern "C" int ast_tpcf_prepare(const void* pos_d, int pos_dtype, const void* ve
     AST_CHECK_ARG(vel_d == nullptr || vel_dtype == AST_F32 || vel_dtype == AST_F64);
     AST_CHECK_ARG(los >= 0 && los <= 2);
     AST_CHECK_ARG(boxsize > 0.0 && std::isfinite(boxsize));
-    AST_CHECK_ARG(n < (size_t(1) << 31));
+    AST_CHECK_ARG(grid_count_ok(n));
     AST_CHECK_ARG(n == 0 || pos_d);
     AST_CHECK_ARG(bounds_d);
     const GridLayout L = tp_layout(1, n, 0, 1);
     AST_CHECK_ARG(work_d && work_bytes >= L.sorted[0]);
     hipStream_t s = ast::as_stream(stream);
-    char* ws = (char*)work_d;
-    GridBounds* box = (GridBounds*)(ws + L.bounds[0]);
-    if (int rc = grid_bounds_reset(box, s)) return rc;
-    if (n > 0) {
-        AST_PROF("tpcf_prep", s);
-        if (int rc = tp_prep(pos_d, pos_dtype, vel_d, vel_dtype, los, boxsize, n, (TpObj*)(ws + L.obj[0]), box, s))
-            return rc;
-    }
-    grid_bounds_kernel<1><<<1, 64, 0, s>>>(box, nullptr, nullptr, bounds_d);
-    AST_CHECK_LAUNCH();
-    return AST_OK;
+    return grid_prepare<1, TpObj>((char*)work_d, L, &n, bounds_d, "tpcf_prep", s, [&](int, TpObj* obj, GridBounds* box) {
+        tp_prep(pos_d, pos_dtype, vel_d, vel_dtype, los, boxsize, n, obj, box, s);
+    });
 }
 
 extern "C" int ast_tpcf_pair_counts(void* work_d, size_t work_bytes, size_t n, double boxsize, int los,
@@ -277,41 +293,17 @@ extern "C" int ast_tpcf_pair_counts(void* work_d, size_t work_bytes, size_t n, d
     AST_CHECK_ARG(bins_ok(ns, nmu));
     AST_CHECK_ARG(los >= 0 && los <= 2);
     AST_CHECK_ARG(boxsize > 0.0 && std::isfinite(boxsize));
-    AST_CHECK_ARG(n < (size_t(1) << 31));
+    AST_CHECK_ARG(grid_count_ok(n));
     AST_CHECK_ARG(s_edges_d && (nmu == 0 || mu_edges_d) && counts_d);
     AST_CHECK_ARG(work_d && work_bytes >= ast_tpcf_workspace_bytes(n, ns, nmu));
     hipStream_t s = ast::as_stream(stream);
     const int nbins = nbins_of(ns, nmu);
-    if (n < 2) {
+    if (grid_no_pairs(1, n, 0)) {
         AST_CHECK_HIP(hipMemsetAsync(counts_d, 0, nbins * sizeof(unsigned long long), s));
         return AST_OK;
     }
-    const GridLayout L = tp_layout(1, n, 0, nbins);
-    char* ws = (char*)work_d;
-    GridBoxParams* prm = (GridBoxParams*)(ws + L.grid);
-    unsigned long long* part = (unsigned long long*)(ws + L.part);
-    {
-        AST_PROF("tpcf_grid", s);
-        tp_plan_kernel<<<1, 64, 0, s>>>(prm, s_edges_d, ns, boxsize, (unsigned)L.cap, single_cell);
-        AST_CHECK_LAUNCH();
-        if (int rc = grid_sort_set<TP_BLOCK, TpObj>(ws, L, 0, n, s)) return rc;
-    }
-    size_t lds;
-    const TpBins bn = tp_bins(boxsize, los, s_edges_d, ns, mu_edges_d, nmu, &lds);
-    AST_CHECK_ARG(lds <= TP_LDS);
-    {
-        AST_PROF("tpcf_pairs", s);
-        tp_pair_kernel<<<TP_GRID, TP_BLOCK, lds, s>>>((const TpObj*)(ws + L.sorted[0]),
-                                                      (const unsigned*)(ws + L.cell_start[0]),
-                                                      (const unsigned*)(ws + L.tile_start[0]), prm, bn, part);
-        AST_CHECK_LAUNCH();
-    }
-    {
-        AST_PROF("tpcf_reduce", s);
-        tp_reduce_kernel<<<(nbins + 255) / 256, 256, 0, s>>>(part, nbins, counts_d);
-        AST_CHECK_LAUNCH();
-    }
-    return AST_OK;
+    return tp_counts(false, (char*)work_d, tp_layout(1, n, 0, nbins), &n, 1, boxsize, los, s_edges_d, ns, mu_edges_d,
+                     nmu, single_cell, counts_d, s);
 }
 
 // ---- two sets, periodic cube or open boundaries
@@ -331,30 +323,20 @@ extern "C" int ast_tpcf_cross_prepare(const void* pos1_d, int pos1_dtype, const 
     AST_CHECK_ARG(vel2_d == nullptr || vel2_dtype == AST_F32 || vel2_dtype == AST_F64);
     AST_CHECK_ARG(los >= 0 && los <= 2);
     AST_CHECK_ARG(boxsize >= 0.0 && std::isfinite(boxsize));
-    AST_CHECK_ARG(n1 < (size_t(1) << 31) && n2 < (size_t(1) << 31));
+    AST_CHECK_ARG(grid_count_ok(n1) && grid_count_ok(n2));
     AST_CHECK_ARG((n1 == 0 || pos1_d) && (n2 == 0 || pos2_d));
     AST_CHECK_ARG(bounds_d);
     const GridLayout L = tp_layout(2, n1, n2, 1);
     AST_CHECK_ARG(work_d && work_bytes >= L.part);
     hipStream_t s = ast::as_stream(stream);
-    char* ws = (char*)work_d;
-    GridBounds* box[2] = {(GridBounds*)(ws + L.bounds[0]), (GridBounds*)(ws + L.bounds[1])};
     const void* pos[2] = {pos1_d, pos2_d};
     const void* vel[2] = {vel1_d, vel2_d};
     const int pos_dtype[2] = {pos1_dtype, pos2_dtype}, vel_dtype[2] = {vel1_dtype, vel2_dtype};
     const size_t n[2] = {n1, n2};
-    {
-        AST_PROF("tpcf_cross_prep", s);
-        for (int q = 0; q < 2; ++q) {
-            if (int rc = grid_bounds_reset(box[q], s)) return rc;
-            if (int rc = tp_prep(pos[q], pos_dtype[q], vel[q], vel_dtype[q], los, boxsize, n[q],
-                                 (TpObj*)(ws + L.obj[q]), box[q], s))
-                return rc;
-        }
-    }
-    grid_bounds_kernel<2><<<1, 64, 0, s>>>(box[0], box[1], &((GridBoxParams*)(ws + L.grid))->box, bounds_d);
-    AST_CHECK_LAUNCH();
-    return AST_OK;
+    return grid_prepare<2, TpObj>((char*)work_d, L, n, bounds_d, "tpcf_cross_prep", s,
+                                  [&](int q, TpObj* obj, GridBounds* box) {
+        tp_prep(pos[q], pos_dtype[q], vel[q], vel_dtype[q], los, boxsize, n[q], obj, box, s);
+    });
 }
 
 extern "C" int ast_tpcf_cross_counts(void* work_d, size_t work_bytes, size_t n1, size_t n2, int auto_pairs,
@@ -364,43 +346,17 @@ extern "C" int ast_tpcf_cross_counts(void* work_d, size_t work_bytes, size_t n1,
     AST_CHECK_ARG(bins_ok(ns, nmu));
     AST_CHECK_ARG(los >= 0 && los <= 2);
     AST_CHECK_ARG(boxsize >= 0.0 && std::isfinite(boxsize));
-    AST_CHECK_ARG(n1 < (size_t(1) << 31) && n2 < (size_t(1) << 31));
+    AST_CHECK_ARG(grid_count_ok(n1) && grid_count_ok(n2));
     AST_CHECK_ARG(s_edges_d && (nmu == 0 || mu_edges_d) && counts_d);
     AST_CHECK_ARG(work_d && work_bytes >= ast_tpcf_cross_workspace_bytes(n1, n2, ns, nmu));
     hipStream_t s = ast::as_stream(stream);
     const int nbins = nbins_of(ns, nmu);
-    if (auto_pairs ? n1 < 2 : (n1 == 0 || n2 == 0)) {
+    if (grid_no_pairs(auto_pairs, n1, n2)) {
         AST_CHECK_HIP(hipMemsetAsync(counts_d, 0, nbins * sizeof(unsigned long long), s));
         return AST_OK;
     }
-    const GridLayout L = tp_layout(2, n1, n2, nbins);
-    char* ws = (char*)work_d;
-    GridBoxParams* prm = (GridBoxParams*)(ws + L.grid);
-    unsigned long long* part = (unsigned long long*)(ws + L.part);
     const size_t n[2] = {n1, n2};
-    const int q2 = auto_pairs ? 0 : 1;
-    {
-        AST_PROF("tpcf_cross_grid", s);
-        tp_plan_kernel<<<1, 64, 0, s>>>(prm, s_edges_d, ns, boxsize, (unsigned)L.cap, single_cell);
-        AST_CHECK_LAUNCH();
-        for (int q = q2; q >= 0; --q)               // set 1 last: its tile count stays in prm->ntiles
-            if (int rc = grid_sort_set<TP_BLOCK, TpObj>(ws, L, q, n[q], s)) return rc;
-    }
-    size_t lds;
-    const TpBins bn = tp_bins(boxsize, los, s_edges_d, ns, mu_edges_d, nmu, &lds);
-    AST_CHECK_ARG(lds <= TP_LDS);
-    {
-        AST_PROF("tpcf_cross_pairs", s);
-        tpx_pair_kernel<<<TP_GRID, TP_BLOCK, lds, s>>>(
-            (const TpObj*)(ws + L.sorted[0]), (const unsigned*)(ws + L.cell_start[0]),
-            (const unsigned*)(ws + L.tile_start[0]), (const TpObj*)(ws + L.sorted[q2]),
-            (const unsigned*)(ws + L.cell_start[q2]), prm, auto_pairs, bn, part);
-        AST_CHECK_LAUNCH();
-    }
-    {
-        AST_PROF("tpcf_cross_reduce", s);
-        tp_reduce_kernel<<<(nbins + 255) / 256, 256, 0, s>>>(part, nbins, counts_d);
-        AST_CHECK_LAUNCH();
-    }
-    return AST_OK;
+    return tp_counts(true, (char*)work_d, tp_layout(2, n1, n2, nbins), n, auto_pairs, boxsize, los, s_edges_d, ns,
+                     mu_edges_d, nmu, single_cell, counts_d, s);
 }
+

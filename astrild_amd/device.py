@@ -1338,6 +1338,66 @@ def bispectrum(field, boxsize, edges, triangles):
     return {"B": b, "ntri": ntri, "k": kmid, "ntri_residual": _tri_cache[key + ("residual",)]}
 
 
+# ------------------------------------------------------------------ pair finders: the host checks they share
+def _real_device(a):
+    """``as_device``, with any dtype but float32 / float64 widened to float64."""
+    t = as_device(a)
+    return t if t.dtype in _REAL else t.to(torch.float64)
+
+
+def _pair_sample(pos, vel, pos_msg, vel_msg, widths=(3,)):
+    """One sample of a pair finder as real device tensors: ``(p, v, n)``, positions (N, 3) and, unless ``vel`` is None,
+    velocities (N, w) with w in ``widths``.  ValueError with ``pos_msg`` / ``vel_msg``, in which ``{p}`` and ``{v}``
+    stand for the two shapes."""
+    p = _real_device(pos)
+    v = None if vel is None else _real_device(vel)
+    n = p.shape[0] if p.dim() == 2 else -1
+    bad_pos = p.shape != (n, 3)
+    if bad_pos or (v is not None and (v.dim() != 2 or v.shape[0] != n or v.shape[1] not in widths)):
+        raise ValueError((pos_msg if bad_pos else vel_msg).format(p=tuple(p.shape), v=v is not None and tuple(v.shape)))
+    return p, v, n
+
+
+def _check_edges(edges, noun, top=None, max_bins=None):
+    """Bin edges as an fp64 array, or ValueError: at least two finite, non-negative, strictly increasing values, at most
+    ``max_bins`` bins, the largest below ``top`` (boxsize / 3 of a periodic box).  ``noun``: "s edge" or "bin edge"."""
+    e = np.asarray(edges, dtype=np.float64).reshape(-1)
+    if len(e) < 2 or not np.all(np.isfinite(e)) or np.any(np.diff(e) <= 0) or e[0] < 0:
+        raise ValueError(f"{noun}s must be at least two finite, non-negative, strictly increasing values")
+    if max_bins is not None and len(e) - 1 > max_bins:
+        raise ValueError(f"{len(e) - 1} bins: at most {max_bins}")
+    if top is not None and not e[-1] < top:
+        raise ValueError(f"the largest {noun} ({e[-1]}) must be below boxsize / 3 ({top})")
+    return e
+
+
+def _positive_real(name, v, echo_float=False):
+    """``float(v)`` of a positive, finite real number (not None, str or bytes), or ValueError naming ``name`` and the
+    value as given, or (``echo_float``) as the float it was read as."""
+    try:
+        x = float("nan") if v is None or isinstance(v, (str, bytes)) else float(v)
+    except (TypeError, ValueError):
+        x = float("nan")
+    if not (np.isfinite(x) and x > 0):
+        raise ValueError(f"{name} must be a positive, finite real number, got {x if echo_float else v!r}")
+    return x
+
+
+def _check_device_bounds(bounds, ns, box, periodic=True, shifted=False):
+    """ValueError unless every non-empty sample lies in the box.  ``bounds``: per sample min x, y, z and max x, y, z as
+    a prepare call returned them (a NaN coordinate counts as -inf and +inf); ``ns``: the sample sizes.  Periodic: all of
+    [0, box]; open boundaries: all finite.  The message numbers the samples when there are two, and says when the
+    bounds are those ``shifted`` into redshift space."""
+    b = np.asarray(bounds).reshape(len(ns), 6)
+    for k, n in enumerate(ns):
+        inside = (np.all(b[k, :3] >= 0.0) and np.all(b[k, 3:] <= box)) if periodic else np.all(np.isfinite(b[k]))
+        if n and not inside:
+            who = "positions" + (f" of sample {k + 1}" if len(ns) > 1 else "") + \
+                (" (after the redshift-space shift)" if shifted else "")
+            rule = f"must lie in [0, {box}]" if periodic else "must be finite"
+            raise ValueError(f"{who} {rule}: min {b[k, :3].tolist()}, max {b[k, 3:].tolist()}")
+
+
 # ------------------------------------------------------------------ mean pairwise velocity
 def pairwise_tv(pos, vel_cart_or_ang, binnr, binwidth, theta1=None, theta2=None):
     """Pair sums of the transverse-velocity pairwise estimator (mean_pairwise_velocity.py, Yasini et al. 2018) on the
@@ -1347,18 +1407,12 @@ def pairwise_tv(pos, vel_cart_or_ang, binnr, binwidth, theta1=None, theta2=None)
     ``max(theta1) > 2 pi``; None: arctan(x / z), arctan(y / z) + 10 deg, as the reference), or (N, 3): cartesian
     already.  numpy arrays or device tensors, float32 or float64 (widened to float64 on load).
     ASTRILD_PV_CELLS=0 forces one cell (all pairs) instead of the cell grid."""
-    import os
     lib = _lib.lib()
     binnr = int(binnr)
     if not 1 <= binnr <= lib.ast_pairwise_max_bins():
         raise ValueError(f"binnr={binnr}: 1..{lib.ast_pairwise_max_bins()} bins")
-    p = as_device(pos)
-    v = as_device(vel_cart_or_ang)
-    p = p if p.dtype in _REAL else p.to(torch.float64)
-    v = v if v.dtype in _REAL else v.to(torch.float64)
-    n = p.shape[0] if p.dim() == 2 else -1
-    if p.shape != (n, 3) or v.dim() != 2 or v.shape[0] != n or v.shape[1] not in (2, 3):
-        raise ValueError(f"pos must be (N, 3) and velocities (N, 2) or (N, 3), got {tuple(p.shape)} and {tuple(v.shape)}")
+    shapes = "pos must be (N, 3) and velocities (N, 2) or (N, 3), got {p} and {v}"
+    p, v, n = _pair_sample(pos, vel_cart_or_ang, shapes, shapes, widths=(2, 3))
     th1 = th2 = None
     mode = 0
     if theta1 is not None and v.shape[1] == 2:
@@ -1397,12 +1451,7 @@ def check_pairwise_pdf_args(pos_shape, vel_shape, r, dist_bin, vel_bin, kind, di
     if n >= 1 << 31:
         raise ValueError(f"N={n}: fewer than 2^31 objects")
     for name, v in (("r", r), ("dist_width", dist_width), ("vel_width", vel_width)):
-        try:
-            v = float("nan") if isinstance(v, (str, bytes)) else float(v)
-        except (TypeError, ValueError):
-            v = float("nan")
-        if not (np.isfinite(v) and v > 0):
-            raise ValueError(f"{name} must be a positive, finite real number, got {v!r}")
+        _positive_real(name, v, echo_float=True)
     if not np.float32(r) > 0:
         raise ValueError(f"r={r} is not positive as a float32, the reference's type of r")
     ints = dict(dist_bin=dist_bin, vel_bin=vel_bin, ffirst=ffirst, ssecond=n if ssecond is None else ssecond)
@@ -1436,14 +1485,10 @@ def pairwise_velocity_pdf(pos, vel, r, dist_bin, vel_bin, kind, dist_width=1.0, 
     to float64 on load).  ValueError, before any library call, for bad arguments.
     ASTRILD_PVPDF_CELLS=0 forces one cell (all pairs) instead of the cell grid; ASTRILD_PVPDF_LDS=0 forces the
     histogram into global memory, whatever its size."""
-    import os
     n, dist_bin, vel_bin, ffirst, ssecond = check_pairwise_pdf_args(
         np.shape(pos), np.shape(vel), r, dist_bin, vel_bin, kind, dist_width, vel_width, ffirst, ssecond, moments)
     lib = _lib.lib()
-    p = as_device(pos)
-    v = as_device(vel)
-    p = p if p.dtype in _REAL else p.to(torch.float64)
-    v = v if v.dtype in _REAL else v.to(torch.float64)
+    p, v = _real_device(pos), _real_device(vel)
     single = os.environ.get("ASTRILD_PVPDF_CELLS", "1") == "0"
     force_global = os.environ.get("ASTRILD_PVPDF_LDS", "1") == "0"
     ws_bytes = lib.ast_pairwise_pdf_workspace_bytes(n, dist_bin, vel_bin, int(bool(moments)))
@@ -1476,11 +1521,7 @@ def check_tpcf_edges(s_edges, mu_edges, boxsize, periodic=True):
         boxsize = float(boxsize)
         if not (np.isfinite(boxsize) and boxsize > 0):
             raise ValueError(f"boxsize must be positive and finite, got {boxsize}")
-    s = np.asarray(s_edges, dtype=np.float64).reshape(-1)
-    if len(s) < 2 or not np.all(np.isfinite(s)) or np.any(np.diff(s) <= 0) or s[0] < 0:
-        raise ValueError("s edges must be at least two finite, non-negative, strictly increasing values")
-    if periodic and not s[-1] < boxsize / 3.0:
-        raise ValueError(f"the largest s edge ({s[-1]}) must be below boxsize / 3 ({boxsize / 3.0})")
+    s = _check_edges(s_edges, "s edge", top=boxsize / 3.0 if periodic else None)
     mu = None
     if mu_edges is not None:
         mu = np.asarray(mu_edges, dtype=np.float64).reshape(-1)
@@ -1500,57 +1541,47 @@ def tpcf_pair_counts(pos, boxsize, s_edges, mu_edges=None, vel=None, los=2):
     ``pos`` / ``vel``: (N, 3), numpy arrays or device tensors, float32 or float64.  ValueError (before any GPU work)
     for bad edges or ``los``, and (from the device bounds) for shifted positions outside [0, boxsize].
     ASTRILD_TPCF_CELLS=0 forces one cell (all pairs) instead of the cell grid."""
-    import os
     s, mu = check_tpcf_edges(s_edges, mu_edges, boxsize)
     if los not in (0, 1, 2):
         raise ValueError(f"los must be 0, 1 or 2, got {los}")
-    boxsize = float(boxsize)
+    one = _pair_sample(pos, vel, "pos must be (N, 3), got {p}", "vel must be (N, 3) like pos, got {v}")
+    return _tpcf_counts([one], None, s, mu, float(boxsize), True, los)
+
+
+def _tpcf_counts(sets, auto, s, mu, box, periodic, los):
+    """The calls of tpcf_pair_counts (``sets``: its one ``_pair_sample``; ast_tpcf_prepare / ast_tpcf_pair_counts) and
+    of tpcf_cross_counts (two, the second (None, None, 0) for ``auto``; ast_tpcf_cross_prepare / ast_tpcf_cross_counts),
+    with the check of the device bounds between the two."""
     lib = _lib.lib()
-    p = as_device(pos)
-    p = p if p.dtype in _REAL else p.to(torch.float64)
-    n = p.shape[0] if p.dim() == 2 else -1
-    if p.shape != (n, 3):
-        raise ValueError(f"pos must be (N, 3), got {tuple(p.shape)}")
-    v = None
-    if vel is not None:
-        v = as_device(vel)
-        v = v if v.dtype in _REAL else v.to(torch.float64)
-        if v.shape != (n, 3):
-            raise ValueError(f"vel must be (N, 3) like pos, got {tuple(v.shape)}")
+    cross = len(sets) == 2
+    sizes = [n for _, _, n in sets]
     ns, nmu = len(s) - 1, 0 if mu is None else len(mu) - 1
     single = os.environ.get("ASTRILD_TPCF_CELLS", "1") == "0"
-    ws_bytes = lib.ast_tpcf_workspace_bytes(n, ns, nmu)
-    work = torch.empty(ws_bytes, dtype=torch.uint8, device=p.device)
-    bounds = torch.empty(6, dtype=torch.float64, device=p.device)
+    device_ = sets[0][0].device
+    ws_bytes = (lib.ast_tpcf_cross_workspace_bytes if cross else lib.ast_tpcf_workspace_bytes)(*sizes, ns, nmu)
+    work = torch.empty(ws_bytes, dtype=torch.uint8, device=device_)
+    bounds = torch.empty(6 * len(sets), dtype=torch.float64, device=device_)
     st = stream()
-    check(lib.ast_tpcf_prepare(ptr(p), real_code(p), ptr(v), real_code(v) if v is not None else F64, los, boxsize, n,
-                               ptr(work), ws_bytes, ptr(bounds), st), "ast_tpcf_prepare")
-    b = to_numpy(bounds)
-    if n and not (np.all(b[:3] >= 0.0) and np.all(b[3:] <= boxsize)):
-        raise ValueError(f"positions (after the redshift-space shift) must lie in [0, {boxsize}]: "
-                         f"min {b[:3].tolist()}, max {b[3:].tolist()}")
+    code = lambda t: real_code(t) if t is not None else F64
+    if cross:
+        (p1, v1, n1), (p2, v2, n2) = sets
+        check(lib.ast_tpcf_cross_prepare(ptr(p1), code(p1), ptr(v1), code(v1), n1, ptr(p2), code(p2), ptr(v2), code(v2),
+                                         n2, los, box, ptr(work), ws_bytes, ptr(bounds), st), "ast_tpcf_cross_prepare")
+    else:
+        p, v, n = sets[0]
+        check(lib.ast_tpcf_prepare(ptr(p), code(p), ptr(v), code(v), los, box, n, ptr(work), ws_bytes, ptr(bounds), st),
+              "ast_tpcf_prepare")
+    _check_device_bounds(to_numpy(bounds), sizes, box, periodic, shifted=True)
     s_d = as_device(s)
     mu_d = as_device(mu) if mu is not None else None
-    counts = torch.empty((ns, nmu) if nmu else (ns,), dtype=torch.int64, device=p.device)
-    check(lib.ast_tpcf_pair_counts(ptr(work), ws_bytes, n, boxsize, los, ptr(s_d), ns, ptr(mu_d), nmu, int(single),
-                                   ptr(counts), st), "ast_tpcf_pair_counts")
+    counts = torch.empty((ns, nmu) if nmu else (ns,), dtype=torch.int64, device=device_)
+    if cross:
+        check(lib.ast_tpcf_cross_counts(ptr(work), ws_bytes, n1, n2, int(auto), box, los, ptr(s_d), ns, ptr(mu_d), nmu,
+                                        int(single), ptr(counts), st), "ast_tpcf_cross_counts")
+    else:
+        check(lib.ast_tpcf_pair_counts(ptr(work), ws_bytes, n, box, los, ptr(s_d), ns, ptr(mu_d), nmu, int(single),
+                                       ptr(counts), st), "ast_tpcf_pair_counts")
     return counts
-
-
-def _tpcf_set(pos, vel, name):
-    """(N, 3) positions and optional velocities of one sample as real device tensors, or ValueError."""
-    p = as_device(pos)
-    p = p if p.dtype in _REAL else p.to(torch.float64)
-    n = p.shape[0] if p.dim() == 2 else -1
-    if p.shape != (n, 3):
-        raise ValueError(f"{name} must be (N, 3), got {tuple(p.shape)}")
-    v = None
-    if vel is not None:
-        v = as_device(vel)
-        v = v if v.dtype in _REAL else v.to(torch.float64)
-        if v.shape != (n, 3):
-            raise ValueError(f"the velocities of {name} must be (N, 3) like it, got {tuple(v.shape)}")
-    return p, v, n
 
 
 def tpcf_cross_counts(pos1, pos2, s_edges, mu_edges=None, boxsize=None, vel1=None, vel2=None, los=2):
@@ -1563,43 +1594,17 @@ def tpcf_cross_counts(pos1, pos2, s_edges, mu_edges=None, boxsize=None, vel1=Non
     (before any pair work) for bad edges (the top s edge is bounded by boxsize / 3 only when periodic), shapes or
     ``los``, and from the device bounds: periodic, shifted coordinates outside [0, boxsize]; open, any non-finite
     coordinate.  ASTRILD_TPCF_CELLS=0 forces one cell (all pairs) instead of the cell grid."""
-    import os
     periodic = boxsize is not None
     s, mu = check_tpcf_edges(s_edges, mu_edges, boxsize, periodic=periodic)
     if los not in (0, 1, 2):
         raise ValueError(f"los must be 0, 1 or 2, got {los}")
-    box = float(boxsize) if periodic else 0.0
-    lib = _lib.lib()
     auto = pos2 is None
     if auto and vel2 is not None:
         raise ValueError("vel2 given without pos2")
-    p1, v1, n1 = _tpcf_set(pos1, vel1, "pos1")
-    p2, v2, n2 = (None, None, 0) if auto else _tpcf_set(pos2, vel2, "pos2")
-    ns, nmu = len(s) - 1, 0 if mu is None else len(mu) - 1
-    single = os.environ.get("ASTRILD_TPCF_CELLS", "1") == "0"
-    ws_bytes = lib.ast_tpcf_cross_workspace_bytes(n1, n2, ns, nmu)
-    work = torch.empty(ws_bytes, dtype=torch.uint8, device=p1.device)
-    bounds = torch.empty(12, dtype=torch.float64, device=p1.device)
-    st = stream()
-    code = lambda t: real_code(t) if t is not None else F64
-    check(lib.ast_tpcf_cross_prepare(ptr(p1), code(p1), ptr(v1), code(v1), n1, ptr(p2), code(p2), ptr(v2), code(v2), n2,
-                                     los, box, ptr(work), ws_bytes, ptr(bounds), st), "ast_tpcf_cross_prepare")
-    b = to_numpy(bounds).reshape(2, 6)
-    for k, n in enumerate((n1, n2)):
-        if not n:
-            continue
-        if periodic and not (np.all(b[k, :3] >= 0.0) and np.all(b[k, 3:] <= box)):
-            raise ValueError(f"positions of sample {k + 1} (after the redshift-space shift) must lie in [0, {box}]: "
-                             f"min {b[k, :3].tolist()}, max {b[k, 3:].tolist()}")
-        if not periodic and not np.all(np.isfinite(b[k])):
-            raise ValueError(f"positions of sample {k + 1} (after the redshift-space shift) must be finite: "
-                             f"min {b[k, :3].tolist()}, max {b[k, 3:].tolist()}")
-    s_d = as_device(s)
-    mu_d = as_device(mu) if mu is not None else None
-    counts = torch.empty((ns, nmu) if nmu else (ns,), dtype=torch.int64, device=p1.device)
-    check(lib.ast_tpcf_cross_counts(ptr(work), ws_bytes, n1, n2, int(auto), box, los, ptr(s_d), ns, ptr(mu_d), nmu,
-                                    int(single), ptr(counts), st), "ast_tpcf_cross_counts")
-    return counts
+    sample = lambda pos, vel, name: _pair_sample(pos, vel, name + " must be (N, 3), got {p}",
+                                                 "the velocities of " + name + " must be (N, 3) like it, got {v}")
+    sets = [sample(pos1, vel1, "pos1"), (None, None, 0) if auto else sample(pos2, vel2, "pos2")]
+    return _tpcf_counts(sets, auto, s, mu, float(boxsize) if periodic else 0.0, periodic, los)
 
 
 # ------------------------------------------------------------------ pairwise-velocity moments in a box
@@ -1621,21 +1626,10 @@ def check_pair_velocity_args(pos1_shape, vel1_shape, edges, pos2_shape=None, vel
         box = float(boxsize)
         if not (np.isfinite(box) and box > 0):
             raise ValueError(f"boxsize must be positive and finite, got {box}")
-    e = np.asarray(edges, dtype=np.float64).reshape(-1)
-    if len(e) < 2 or not np.all(np.isfinite(e)) or np.any(np.diff(e) <= 0) or e[0] < 0:
-        raise ValueError("bin edges must be at least two finite, non-negative, strictly increasing values")
-    if len(e) - 1 > _lib.PAIRVEL_MAX_BINS:
-        raise ValueError(f"{len(e) - 1} bins: at most {_lib.PAIRVEL_MAX_BINS}")
-    if periodic and not e[-1] < box / 3.0:
-        raise ValueError(f"the largest bin edge ({e[-1]}) must be below boxsize / 3 ({box / 3.0})")
+    e = _check_edges(edges, "bin edge", top=box / 3.0 if periodic else None, max_bins=_lib.PAIRVEL_MAX_BINS)
     pmax = 0.0
     if kind == "los":
-        try:
-            pmax = float("nan") if pi_max is None or isinstance(pi_max, (str, bytes)) else float(pi_max)
-        except (TypeError, ValueError):
-            pmax = float("nan")
-        if not (np.isfinite(pmax) and pmax > 0):
-            raise ValueError(f"pi_max must be a positive, finite real number, got {pi_max!r}")
+        pmax = _positive_real("pi_max", pi_max)
         if periodic and not pmax < box / 3.0:
             raise ValueError(f"pi_max ({pmax}) must be below boxsize / 3 ({box / 3.0})")
     if pos2_shape is None and vel2_shape is not None:
@@ -1677,12 +1671,8 @@ def pair_velocity_moments(pos1, vel1, edges, pos2=None, vel2=None, boxsize=None,
     periodic = boxsize is not None
     auto = pos2 is None
     lib = _lib.lib()
-    sets = []
-    for a in (pos1, vel1) + (() if auto else (pos2, vel2)):
-        t = as_device(a)
-        sets.append(t if t.dtype in _REAL else t.to(torch.float64))
-    p1, v1 = sets[0], sets[1]
-    p2, v2 = (None, None) if auto else (sets[2], sets[3])
+    p1, v1 = _real_device(pos1), _real_device(vel1)
+    p2, v2 = (None, None) if auto else (_real_device(pos2), _real_device(vel2))
     nb = len(e) - 1
     single = os.environ.get("ASTRILD_PAIRVEL_CELLS", "1") == "0"
     ws_bytes = lib.ast_pairvel_workspace_bytes(n1, n2, nb)
@@ -1692,16 +1682,7 @@ def pair_velocity_moments(pos1, vel1, edges, pos2=None, vel2=None, boxsize=None,
     code = lambda t: real_code(t) if t is not None else F64
     check(lib.ast_pairvel_prepare(ptr(p1), code(p1), ptr(v1), code(v1), n1, ptr(p2), code(p2), ptr(v2), code(v2), n2,
                                   ptr(work), ws_bytes, ptr(bounds), st), "ast_pairvel_prepare")
-    b = to_numpy(bounds).reshape(2, 6)
-    for k, n in enumerate((n1, n2)):
-        if not n:
-            continue
-        if periodic and not (np.all(b[k, :3] >= 0.0) and np.all(b[k, 3:] <= box)):
-            raise ValueError(f"positions of sample {k + 1} must lie in [0, {box}]: "
-                             f"min {b[k, :3].tolist()}, max {b[k, 3:].tolist()}")
-        if not periodic and not np.all(np.isfinite(b[k])):
-            raise ValueError(f"positions of sample {k + 1} must be finite: "
-                             f"min {b[k, :3].tolist()}, max {b[k, 3:].tolist()}")
+    _check_device_bounds(to_numpy(bounds), (n1, n2), box, periodic)
     e_d = as_device(e)
     count = torch.empty(nb, dtype=torch.int64, device=p1.device)
     s1 = torch.empty(nb, dtype=torch.float64, device=p1.device)
