@@ -201,6 +201,13 @@ SIGNATURES = {
     "ast_grid_divergence": (_i, [_vp, _vp, _i, _sz, _sz, _sz, _d, _i, _i, _vp]),
     "ast_vector_magnitude": (_i, [_vp, _vp, _i, _sz, _vp]),
     "ast_spectral_divergence": (_i, [_vp, _vp, _vp, _vp, _i, _i, _d, _vp]),
+    "ast_watershed_max_passes": (_i, [_i]),
+    "ast_watershed_link": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
+    "ast_watershed_jump": (_i, [_vp, _i, _vp, ct.POINTER(_i), _vp]),
+    "ast_watershed_relabel": (_i, [_vp, _vp, _sz, _sz, _vp, _vp]),
+    "ast_watershed_sums": (_i, [_vp, _i, _vp, _i, _sz, _vp, _vp, _vp]),
+    "ast_watershed_edge_blocks": (_sz, [_i]),
+    "ast_watershed_edges": (_i, [_vp, _i, _vp, _i, _vp, _sz, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -2026,6 +2026,171 @@ def tunnels_circles(records, x_pix, y_pix):
     return X / W, Y / W, np.hypot(ux, uy) / W
 
 
+# ------------------------------------------------------------------ watershed void finder
+WATERSHED_INT_SUMS = ("area", "sum_x", "sum_y", "edge_pix")
+
+
+def check_watershed_map(img):
+    """The argument checks of ``watershed_basins``, before any GPU work: a square 2D float32 / float64 map (numpy array
+    or tensor) with 3 <= npix and npix^2 < 2^31.  Returns ``(npix, on_device)`` or raises ValueError."""
+    on_device = isinstance(img, torch.Tensor)
+    if not on_device:
+        img = np.asarray(img)
+    shape = tuple(int(s) for s in img.shape)
+    if len(shape) != 2 or shape[0] != shape[1]:
+        raise ValueError(f"a square 2D map is expected, got shape {shape}")
+    floating = img.dtype in (torch.float32, torch.float64) if on_device else img.dtype in (np.float32, np.float64)
+    if not floating:
+        raise ValueError(f"the map must be float32 or float64, got {img.dtype}")
+    npix = shape[0]
+    if npix < 3 or npix * npix >= 1 << 31:
+        raise ValueError(f"npix={npix}: 3 <= npix and npix^2 < 2^31 are required")
+    return npix, on_device
+
+
+def watershed_basins(img, return_passes=False):
+    """The watershed basins of a square map (``ast_watershed_*``).  Pixels are ordered by (f[p], p) with
+    p = y npix + x, values compared in the map's dtype; every pixel links to the smallest of itself and its up-to-8
+    neighbours inside the map; a basin is the set of pixels whose links end at the same minimum.  Returns a dict:
+
+    * ``labels`` (npix, npix) int32: the basin of every pixel, basins numbered 0 .. M - 1 in ascending flat index of
+      their minimum;
+    * ``minima`` (M,) int64 flat indices, ``f_min`` (M,) their values in the map's dtype;
+    * ``area``, ``sum_x``, ``sum_y``, ``edge_pix`` (M,) int64: pixel count, sums of column and row, pixels on the
+      outermost rows / columns; ``sum_f`` (M,) float64 (atomic additions: the last bits may differ between calls);
+    * ``edges`` (E, 2) int32 pairs a < b of basins with 8-adjacent pixels, sorted by (a, b), and ``saddle`` (E,) in the
+      map's dtype: the minimum over those pixel pairs of max(f[p], f[q]) (a zero saddle is +0.0).
+
+    A numpy array gives numpy arrays, a device tensor device tensors; the map is not changed.  ValueError before any
+    launch for a map that is not square, float32 / float64 and of 3 <= npix, npix^2 < 2^31, and with no result when the
+    device finds a NaN or an infinity in it.  ``return_passes``: ``(dict, pointer-jumping passes taken)``."""
+    npix, on_device = check_watershed_map(img)
+    lib = _lib.lib()
+    t = as_device(img)
+    code, n = real_code(t), npix * npix
+    link = torch.empty(n, dtype=torch.int32, device=t.device)
+    count = torch.empty(1, dtype=torch.int64, device=t.device)
+    check(lib.ast_watershed_link(ptr(t), code, npix, ptr(link), ptr(count), stream()), "ast_watershed_link")
+    bad = int(count.item())
+    if bad:
+        raise ValueError(f"the map holds {bad} pixels that are NaN or infinite")
+    pending = torch.empty(lib.ast_watershed_max_passes(npix), dtype=torch.int32, device=t.device)
+    passes = ct.c_int(0)
+    check(lib.ast_watershed_jump(ptr(link), npix, ptr(pending), ct.byref(passes), stream()), "ast_watershed_jump")
+    # compact ids in ascending index of the minimum (torch: plumbing), then labels = id[minimum of the pixel]
+    minima = torch.nonzero(link == torch.arange(n, dtype=torch.int32, device=t.device)).reshape(-1)
+    m = int(minima.numel())
+    ids = torch.empty(n, dtype=torch.int32, device=t.device)        # read at minima only
+    ids[minima] = torch.arange(m, dtype=torch.int32, device=t.device)
+    labels = torch.empty(n, dtype=torch.int32, device=t.device)
+    check(lib.ast_watershed_relabel(ptr(link), ptr(ids), n, n, ptr(labels), stream()), "ast_watershed_relabel")
+    del link, ids
+    isums = torch.empty((4, m), dtype=torch.int64, device=t.device)
+    sum_f = torch.empty(m, dtype=torch.float64, device=t.device)
+    check(lib.ast_watershed_sums(ptr(t), code, ptr(labels), npix, m, ptr(isums), ptr(sum_f), stream()),
+          "ast_watershed_sums")
+    # boundary pairs: count, allocate exactly, fill; then one minimum per pair (sort and segment minimum in torch)
+    blocks = torch.empty(lib.ast_watershed_edge_blocks(npix), dtype=torch.int64, device=t.device)
+    check(lib.ast_watershed_edges(ptr(t), code, ptr(labels), npix, ptr(blocks), 0, None, None, stream()),
+          "ast_watershed_edges")
+    ends = torch.cumsum(blocks, 0)
+    nrec = int(ends[-1].item())
+    if nrec:
+        first = ends - blocks                        # every tile's first record
+        keys = torch.empty(nrec, dtype=torch.int64, device=t.device)
+        sad = torch.empty(nrec, dtype=t.dtype, device=t.device)
+        check(lib.ast_watershed_edges(ptr(t), code, ptr(labels), npix, ptr(first), nrec, ptr(keys), ptr(sad), stream()),
+              "ast_watershed_edges")
+        keys, order = torch.sort(keys)
+        pairs, inverse = torch.unique_consecutive(keys, return_inverse=True)
+        saddle = torch.full((int(pairs.numel()),), float("inf"), dtype=t.dtype, device=t.device)
+        saddle = saddle.scatter_reduce(0, inverse, sad[order], "amin")
+        edges = torch.stack([pairs >> 32, pairs & 0xFFFFFFFF], dim=1).to(torch.int32)
+    else:
+        edges = torch.zeros((0, 2), dtype=torch.int32, device=t.device)
+        saddle = torch.zeros(0, dtype=t.dtype, device=t.device)
+    out = {"labels": labels.view(npix, npix), "minima": minima, "f_min": t.reshape(-1)[minima],
+           "area": isums[0], "sum_x": isums[1], "sum_y": isums[2], "edge_pix": isums[3], "sum_f": sum_f,
+           "edges": edges, "saddle": saddle}
+    if not on_device:
+        out = {k: to_numpy(v.contiguous()) for k, v in out.items()}
+    return (out, passes.value) if return_passes else out
+
+
+def _host(v):
+    return to_numpy(v) if isinstance(v, torch.Tensor) else np.asarray(v)
+
+
+def watershed_merge(basins, h):
+    """Merge the basins of ``watershed_basins`` at height ``h`` >= 0 (persistence), on the host.  The edges are taken
+    in ascending (saddle, a, b); with ra, rb the current roots of a and b, ra != rb, the two sets merge iff
+    saddle - max(m_ra, m_rb) < h in float64, m_r being the lowest minimum of the root's set, and the root of the
+    merged set is the one with the smaller (m, id).  h = 0 merges nothing, h = inf every connected pair.  Every final
+    set is a void; voids are numbered in ascending id of their root basin.  Returns a dict of numpy arrays:
+    ``void_of_basin`` (M,) int32, and per void ``root`` (basin id), ``area``, ``sum_x``, ``sum_y``, ``edge_pix`` (int64),
+    ``sum_f`` (float64), ``kappa_min`` (the root's minimum, map dtype) and ``min_index`` (its flat pixel index)."""
+    h = float(h)
+    if not h >= 0.0:
+        raise ValueError(f"the merge height must be >= 0, got {h}")
+    f_min, minima = _host(basins["f_min"]), _host(basins["minima"])
+    edges, saddle = _host(basins["edges"]).reshape(-1, 2), _host(basins["saddle"])
+    m = len(f_min)
+    depth = f_min.astype(np.float64)                # exact for float32
+    parent = list(range(m))
+    low = depth.tolist()                            # lowest minimum of each root's set; the root is where it sits
+
+    def find(i):
+        root = i
+        while parent[root] != root:
+            root = parent[root]
+        while parent[i] != root:
+            parent[i], i = root, parent[i]
+        return root
+
+    if h > 0.0 and len(edges):
+        s64 = saddle.astype(np.float64)
+        for e in np.lexsort((edges[:, 1], edges[:, 0], s64)):
+            ra, rb = find(int(edges[e, 0])), find(int(edges[e, 1]))
+            if ra == rb:
+                continue
+            if float(s64[e]) - max(low[ra], low[rb]) < h:
+                keep, gone = (ra, rb) if (low[ra], ra) < (low[rb], rb) else (rb, ra)
+                parent[gone] = keep
+    root_of = np.array([find(i) for i in range(m)], dtype=np.int64)
+    roots, void_of_basin = np.unique(root_of, return_inverse=True)
+    out = {"void_of_basin": void_of_basin.astype(np.int32).reshape(-1), "root": roots}
+    for k in WATERSHED_INT_SUMS:
+        out[k] = _segment_sum_int(void_of_basin, _host(basins[k]), len(roots))
+    out["sum_f"] = np.bincount(void_of_basin.reshape(-1), weights=_host(basins["sum_f"]), minlength=len(roots))
+    out["kappa_min"] = f_min[roots]
+    out["min_index"] = minima[roots].astype(np.int64)
+    return out
+
+
+def _segment_sum_int(index, values, nseg):
+    out = np.zeros(nseg, dtype=np.int64)
+    np.add.at(out, np.asarray(index).reshape(-1), np.asarray(values, dtype=np.int64))
+    return out
+
+
+def watershed_void_map(basins, void_of_basin):
+    """The (npix, npix) int32 map of void ids: ``basins["labels"]`` through the basin -> void table of
+    ``watershed_merge`` (``ast_watershed_relabel``).  Numpy labels give a numpy map, device labels a device map."""
+    labels = basins["labels"]
+    on_device = isinstance(labels, torch.Tensor)
+    table = np.ascontiguousarray(_host(void_of_basin), dtype=np.int32).reshape(-1)
+    if len(table) == 0:
+        raise ValueError("void_of_basin is empty")
+    lab = as_device(labels, torch.int32)
+    if lab.dim() != 2 or lab.shape[0] != lab.shape[1]:
+        raise ValueError(f"labels must be a square map, got shape {tuple(lab.shape)}")
+    tab = as_device(table)
+    out = torch.empty_like(lab)
+    check(_lib.lib().ast_watershed_relabel(ptr(lab), ptr(tab), tab.numel(), lab.numel(), ptr(out), stream()),
+          "ast_watershed_relabel")
+    return out if on_device else to_numpy(out)
+
+
 # ------------------------------------------------------------------ vector grids
 def check_divergence_args(shape, dtype, spacing):
     """The argument checks of ``divergence``, host only: ``shape`` (n0, n1, n2, 3) with every side >= 3, ``dtype``

@@ -1,1 +1,2 @@
 from .tunnel import TunnelsFinder, TunnelsFinderWarning  # noqa: F401
+from .watershed import WatershedFinder, WatershedFinderWarning  # noqa: F401

@@ -33,6 +33,7 @@ extern "C" {
 #define AST_ERR_HIP (-2)
 #define AST_ERR_ROCFFT (-3)
 #define AST_ERR_WORKSPACE (-4)
+#define AST_ERR_LIMIT (-5) /* a bounded iteration did not end within its bound */
 
 #define AST_F32 0
 #define AST_F64 1
@@ -1129,6 +1130,44 @@ int ast_vector_magnitude(const void* v_d, void* out_d, int dtype, size_t count, 
  * may be cx_d.  No reference counterpart (the reference differentiates in real space only). */
 int ast_spectral_divergence(const void* cx_d, const void* cy_d, const void* cz_d, void* out_d, int cdtype, int nmesh,
                             double boxsize, void* stream);
+
+/* ------------------------------------------------- watershed void finder */
+
+/* The watershed void finder of rays/voids/watershed.py (which in the reference only writes files for an external
+ * program; rays/utils/watershed_voids.py does not run).  Defined in DESIGN.md 6j: pixels of an npix x npix map
+ * (AST_F32 / AST_F64, 3 <= npix, npix^2 < 2^31, flat index p = y npix + x) are totally ordered by (f[p], p), values
+ * compared in the map's dtype; link[p] is the smallest of p and its up-to-8 neighbours inside the map; a minimum has
+ * link[p] == p, and following links from p ends at the minimum of p's basin.
+ *
+ * ast_watershed_link writes link_d[npix^2] (int32) and *nonfinite_d (device uint64) = the number of NaN / inf pixels,
+ * which the caller must find 0 before it goes on.
+ * ast_watershed_jump resolves link_d in place to link[p] = the minimum of p's basin, by pointer jumping, at most
+ * ast_watershed_max_passes(npix) = ceil(log2(npix^2)) passes (0: npix out of range), fewer when a pass reports that
+ * every entry points at a minimum.  pending_d: that many int32 of device scratch.  *passes_host receives the number
+ * of passes taken.  SYNCHRONOUS (one 4-byte read-back per pass).  AST_ERR_LIMIT when the bound did not suffice, which
+ * no output of ast_watershed_link can cause.
+ * ast_watershed_relabel: out_d[i] = table_d[src_d[i]], i < n (int32; -1 for an index outside [0, table_len)); out_d
+ * may be src_d.  It makes the compact basin ids from the resolved links and the void map from the basin labels.
+ * ast_watershed_sums: labels_d[npix^2] in [0, nbasins) -> isums_d[4][nbasins] int64 = area, sum of x, sum of y and
+ * the number of pixels on the outermost rows / columns of every basin, sum_f_d[nbasins] = its sum of f in float64
+ * (atomics: the order of the additions is not fixed).  Both are zeroed by the call.
+ * ast_watershed_edges: every pixel looks at its E, SW, S and SE neighbours, so that every 8-adjacent pair is seen
+ * once; for every other label among them it has one record, key (a << 32 | b) with a < b and the smallest
+ * max(f[p], f[q]) + 0 (a -0.0 becomes +0.0) over those neighbours, in the map's dtype.  One 16 x 16 tile per workgroup,
+ * ast_watershed_edge_blocks(npix) = ceil(npix / 16)^2 of them (0: npix out of range).  cap == 0: blocks_d[b] (int64)
+ * receives the number of records of tile b (keys_d, saddle_d unused).  cap > 0: blocks_d[b] GIVES the index of tile
+ * b's first record - the exclusive prefix sum of the counts, which the caller forms, cap being their total - and the
+ * records go to keys_d[cap], saddle_d[cap], never past cap.  No global atomics: count, allocate exactly, fill. */
+int ast_watershed_max_passes(int npix);
+int ast_watershed_link(const void* img_d, int dtype, int npix, int* link_d, unsigned long long* nonfinite_d,
+                       void* stream);
+int ast_watershed_jump(int* link_d, int npix, int* pending_d, int* passes_host, void* stream);
+int ast_watershed_relabel(const int* src_d, const int* table_d, size_t table_len, size_t n, int* out_d, void* stream);
+int ast_watershed_sums(const void* img_d, int dtype, const int* labels_d, int npix, size_t nbasins, long long* isums_d,
+                       double* sum_f_d, void* stream);
+size_t ast_watershed_edge_blocks(int npix);
+int ast_watershed_edges(const void* img_d, int dtype, const int* labels_d, int npix, long long* blocks_d, size_t cap,
+                        long long* keys_d, void* saddle_d, void* stream);
 
 #ifdef __cplusplus
 }
