@@ -26,6 +26,7 @@ PVPDF_MAX_BINS = 1 << 22                    # ast_pairwise_pdf_max_bins(), known
 PVPDF_MAX_MOMENT_ROWS = 480                 # without a library call (AST_PVPDF_MAX_MOMENT_ROWS)
 PAIRVEL_KIND = {"radial": 0, "los": 1}      # AST_PAIRVEL_*
 PAIRVEL_MAX_BINS = 511                      # ast_pairvel_max_bins() (AST_PAIRVEL_MAX_BINS), known here likewise
+TPCF_JK_MAX_TABLE = 1 << 22                 # ast_tpcf_jk_max_table(): regions x bins of a jackknife, likewise
 
 
 class AstrildHipError(RuntimeError):
@@ -177,6 +178,12 @@ SIGNATURES = {
     "ast_tpcf_cross_workspace_bytes": (_sz, [_sz, _sz, _i, _i]),
     "ast_tpcf_cross_prepare": (_i, [_vp, _i, _vp, _i, _sz, _vp, _i, _vp, _i, _sz, _i, _d, _vp, _sz, _vp, _vp]),
     "ast_tpcf_cross_counts": (_i, [_vp, _sz, _sz, _sz, _i, _d, _i, _vp, _i, _vp, _i, _i, _vp, _vp]),
+    "ast_tpcf_jk_workspace_bytes": (_sz, [_sz, _sz, _i, _i, _i]),
+    "ast_tpcf_jk_max_table": (_i, []),
+    "ast_tpcf_jk_lds_table": (_i, [_i, _i]),
+    "ast_tpcf_jk_prepare": (_i, [_vp, _i, _vp, _i, _vp, _sz, _vp, _i, _vp, _i, _vp, _sz, _i, _d, _vp, _vp, _vp, _vp, _sz,
+                                 _vp, _vp]),
+    "ast_tpcf_jk_counts": (_i, [_vp, _sz, _sz, _sz, _i, _d, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "ast_pairvel_workspace_bytes": (_sz, [_sz, _sz, _i]),
     "ast_pairvel_max_bins": (_i, []),
     "ast_pairvel_prepare": (_i, [_vp, _i, _vp, _i, _sz, _vp, _i, _vp, _i, _sz, _vp, _sz, _vp, _vp]),

@@ -1607,6 +1607,127 @@ def tpcf_cross_counts(pos1, pos2, s_edges, mu_edges=None, boxsize=None, vel1=Non
     return _tpcf_counts(sets, auto, s, mu, float(boxsize) if periodic else 0.0, periodic, los)
 
 
+def check_jackknife_args(nsub, pos1_shape, pos2_shape=None, tags1_shape=None, tags2_shape=None, extent=None,
+                         boxsize=None, nbins=1):
+    """The argument checks of ``tpcf_jackknife_counts`` that are its own, on the host and without a library call:
+    ``(nsub3, ntot, lo, hi)`` or ValueError.  ``nsub``: an int or three ints >= 1 (anything with ``__index__``, no
+    bools) -> ``nsub3`` and their product ``ntot``, with ``ntot * nbins <= _lib.TPCF_JK_MAX_TABLE``.  Positions (N, 3).
+    Explicit tags: one integer per object, for every sample given or for none, with ``nsub`` a single int (the number
+    of regions, ``nsub3 = (nsub, 1, 1)``) and no ``extent``.  ``extent = (lo, hi)``, each a scalar or three values,
+    finite with hi > lo -> fp64 ``lo``, ``hi`` of three; without one ``[0, boxsize]`` when periodic, else ``None, None``:
+    the caller takes the bounding box of the positions."""
+    import operator
+    shapes = [tuple(pos1_shape)] + ([] if pos2_shape is None else [tuple(pos2_shape)])
+    for k, ps in enumerate(shapes):
+        if len(ps) != 2 or ps[1] != 3:
+            raise ValueError(f"pos{k + 1} must be (N, 3), got {ps}")
+    if pos2_shape is None and tags2_shape is not None:
+        raise ValueError("tags2 given without pos2")
+    tagged = tags1_shape is not None
+    if pos2_shape is not None and (tags2_shape is not None) != tagged:
+        raise ValueError("explicit tags are given for both samples or for neither")
+    try:
+        many = np.ndim(nsub) != 0
+        vals = [operator.index(v) for v in nsub] if many else [operator.index(nsub)]
+        if any(isinstance(v, (bool, np.bool_)) for v in (nsub if many else [nsub])):
+            raise TypeError
+    except TypeError:
+        raise ValueError(f"nsub must be an int or three ints, got {nsub!r}") from None
+    if len(vals) not in (1, 3) or min(vals) < 1:
+        raise ValueError(f"nsub must be one or three integers >= 1, got {nsub!r}")
+    if tagged:
+        if len(vals) != 1:
+            raise ValueError("with explicit tags nsub is the number of regions, a single int")
+        if extent is not None:
+            raise ValueError("extent has no meaning with explicit tags")
+        for k, (ps, ts) in enumerate(zip(shapes, (tags1_shape, tags2_shape))):
+            if tuple(ts) != (ps[0],):
+                raise ValueError(f"tags{k + 1} must be ({ps[0]},), one region per object, got {tuple(ts)}")
+        nsub3 = (vals[0], 1, 1)
+    else:
+        nsub3 = tuple(vals * 3 if len(vals) == 1 else vals)
+    ntot = nsub3[0] * nsub3[1] * nsub3[2]
+    if ntot * int(nbins) > _lib.TPCF_JK_MAX_TABLE:
+        raise ValueError(f"{ntot} regions x {nbins} bins: at most {_lib.TPCF_JK_MAX_TABLE} counters")
+    lo = hi = None
+    if tagged:
+        lo, hi = np.zeros(3), np.ones(3)
+    elif extent is not None:
+        try:
+            lo, hi = (np.broadcast_to(np.asarray(e, dtype=np.float64), (3,)).copy() for e in extent)
+        except (TypeError, ValueError):
+            raise ValueError(f"extent must be (lo, hi), each a scalar or three values, got {extent!r}") from None
+        if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi)) and np.all(hi > lo)):
+            raise ValueError(f"extent must be finite with hi > lo, got lo {lo.tolist()}, hi {hi.tolist()}")
+    elif boxsize is not None:
+        lo, hi = np.zeros(3), np.full(3, float(boxsize))
+    return nsub3, ntot, lo, hi
+
+
+def tpcf_jackknife_counts(pos1, nsub, s_edges, mu_edges=None, pos2=None, boxsize=None, vel1=None, vel2=None, los=2,
+                          tags1=None, tags2=None, extent=None):
+    """The pair counts of tpcf_cross_counts with the endpoint table of a leave-one-region-out jackknife
+    (ast_tpcf_jk_prepare / ast_tpcf_jk_counts): ``(counts, ends)``, int64 device tensors of (ns[, nmu]) and
+    (ntot, ns[, nmu]).  ``counts`` is tpcf_cross_counts' on the same input (``pos2=None``: unordered pairs of ``pos1``);
+    ``ends[k, b]`` is the number of pair ends in region k over the pairs of bin b (both ends in k: 2), so that
+    ``2 counts - ends[k]`` is the ordered auto pairs (twice the cross pairs) with region k left out, a pair weighing
+    1 / 1/2 / 0 with 0 / 1 / 2 ends in k, and ``ends.sum(0) == 2 counts``.  Regions: ``nsub`` an int or three ints,
+    a grid of nsub_x x nsub_y x nsub_z boxes over ``extent = (lo, hi)`` (default: [0, boxsize] when periodic, else the
+    bounding box of the given positions of both samples); an object is in box ``floor((x - lo) / ((hi - lo) / nsub))``
+    per axis of its position AFTER the redshift-space shift, clamped to the grid, numbered in C order (ntot their
+    product).  Or ``tags1`` / ``tags2``: a region in [0, nsub) per object (``nsub`` one int = ntot); a tag out of range
+    is a ValueError from the device check, before any pair work.  Everything else as tpcf_cross_counts, including its
+    ValueErrors; check_jackknife_args holds the host checks of the arguments above.  ASTRILD_TPCF_CELLS=0 forces one
+    cell; ASTRILD_TPCF_JK_LDS=0 forces the table into global memory, whatever its size."""
+    periodic = boxsize is not None
+    s, mu = check_tpcf_edges(s_edges, mu_edges, boxsize, periodic=periodic)
+    if los not in (0, 1, 2):
+        raise ValueError(f"los must be 0, 1 or 2, got {los}")
+    auto = pos2 is None
+    if auto and vel2 is not None:
+        raise ValueError("vel2 given without pos2")
+    ns, nmu = len(s) - 1, 0 if mu is None else len(mu) - 1
+    nsub3, ntot, lo, hi = check_jackknife_args(
+        nsub, np.shape(pos1), None if auto else np.shape(pos2), None if tags1 is None else np.shape(tags1),
+        None if tags2 is None else np.shape(tags2), extent, boxsize, ns * max(nmu, 1))
+    sample = lambda pos, vel, name: _pair_sample(pos, vel, name + " must be (N, 3), got {p}",
+                                                 "the velocities of " + name + " must be (N, 3) like it, got {v}")
+    (p1, v1, n1), (p2, v2, n2) = sample(pos1, vel1, "pos1"), (None, None, 0) if auto else sample(pos2, vel2, "pos2")
+    t1 = None if tags1 is None else as_device(tags1).to(torch.int32)
+    t2 = None if tags2 is None else as_device(tags2).to(torch.int32)
+    if lo is None:
+        filled = [p for p in (p1, p2) if p is not None and p.shape[0]]
+        lo = np.min([to_numpy(p.amin(0)).astype(np.float64) for p in filled], axis=0) if filled else np.zeros(3)
+        hi = np.max([to_numpy(p.amax(0)).astype(np.float64) for p in filled], axis=0) if filled else np.zeros(3)
+        if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi))):
+            raise ValueError(f"positions must be finite: min {lo.tolist()}, max {hi.tolist()}")
+    lib = _lib.lib()
+    box = float(boxsize) if periodic else 0.0
+    single = os.environ.get("ASTRILD_TPCF_CELLS", "1") == "0"
+    force_global = os.environ.get("ASTRILD_TPCF_JK_LDS", "1") == "0"
+    ws_bytes = lib.ast_tpcf_jk_workspace_bytes(n1, n2, ns, nmu, ntot)
+    work = torch.empty(ws_bytes, dtype=torch.uint8, device=p1.device)
+    bounds = torch.empty(13, dtype=torch.float64, device=p1.device)
+    st = stream()
+    code = lambda t: real_code(t) if t is not None else F64
+    nsub_h, lo_h, hi_h = (ct.c_int * 3)(*nsub3), (ct.c_double * 3)(*lo), (ct.c_double * 3)(*hi)
+    check(lib.ast_tpcf_jk_prepare(ptr(p1), code(p1), ptr(v1), code(v1), ptr(t1), n1, ptr(p2), code(p2), ptr(v2), code(v2),
+                                  ptr(t2), n2, los, box, nsub_h, lo_h, hi_h, ptr(work), ws_bytes, ptr(bounds), st),
+          "ast_tpcf_jk_prepare")
+    b = to_numpy(bounds)
+    _check_device_bounds(b[:12], (n1, n2), box, periodic, shifted=True)
+    if b[12] != 0.0:
+        raise ValueError(f"explicit tags must lie in [0, {ntot}), the regions of nsub")
+    s_d = as_device(s)
+    mu_d = as_device(mu) if mu is not None else None
+    shape = (ns, nmu) if nmu else (ns,)
+    counts = torch.empty(shape, dtype=torch.int64, device=p1.device)
+    ends = torch.empty((ntot,) + shape, dtype=torch.int64, device=p1.device)
+    check(lib.ast_tpcf_jk_counts(ptr(work), ws_bytes, n1, n2, int(auto), box, los, ptr(s_d), ns, ptr(mu_d), nmu, ntot,
+                                 int(single), int(force_global), ptr(counts), ptr(ends), st), "ast_tpcf_jk_counts")
+    return counts, ends
+
+
 # ------------------------------------------------------------------ pairwise-velocity moments in a box
 def check_pair_velocity_args(pos1_shape, vel1_shape, edges, pos2_shape=None, vel2_shape=None, boxsize=None,
                              kind="radial", pi_max=None, los=2):

@@ -54,6 +54,10 @@ source fixes it, without a check against the library itself:
   that were needed, under ``D1D1, D1D2, D2D2, D1R, D2R, RR`` (unordered pairs for ``D1D1, D2D2, RR``); otherwise, as
   before, the array of unordered ``D1D1`` counts.
 
+* **Jackknife errors** (``tpcf_jackknife``, halotools' function of that name): xi with the covariance matrix of a
+  leave-one-subvolume-out resampling, every leave-one-out count of a term from one pass over its pairs; the weights,
+  the identity behind the single pass and what is recalled rather than checked are in its docstring.
+
 ``nthreads`` is accepted and ignored.
 """
 from typing import Optional, Union
@@ -93,7 +97,7 @@ def _cross(pos1, pos2, boxsize, s_edges, mu_edges, vel1=None, vel2=None, los=2):
 def _estimate(estimator, dd, dr, rr, na, nb, nr):
     """halotools' ``_TP_estimator`` from ordered pair counts (module docstring); ``dr`` / ``rr`` None when the
     estimator does not use them."""
-    na, nb, nr = float(na), float(nb), float(nr)
+    na, nb, nr = np.float64(na), np.float64(nb), np.float64(nr)      # a size of 0 gives inf / nan, not an exception
     with np.errstate(divide="ignore", invalid="ignore"):
         if estimator == "Natural":
             return (nr * nr) / (na * nb) * dd / rr - 1.0
@@ -303,6 +307,143 @@ def s_mu_tpcf(sample1, s_bins, mu_bins, sample2=None, randoms=None, period=None,
     s, mu = dev.check_tpcf_edges(s_bins, mu_bins, period, periodic=period is not None)
     xi, c = _correlate(sample1, sample2, randoms, s, mu, period, estimator, do_auto, do_cross, los=los)
     return (xi, c) if return_counts else xi
+
+
+def jackknife_tags(pos, nsub, lo, hi):
+    """The jackknife region of every object, int32 (N,): per axis ``i = floor((x - lo) / ((hi - lo) / nsub))`` in fp64
+    with true divisions, clamped to ``[0, nsub - 1]`` on both sides (``x == hi``, a point outside ``[lo, hi]`` and a NaN
+    belong to a border region), and ``tag = (i_x nsub_y + i_y) nsub_z + i_z``: numpy's C order, halotools' label
+    minus one.  ``nsub``, ``lo``, ``hi``: three values each.  Host numpy; the rule of ``ast_tpcf_jk_prepare``."""
+    x = np.asarray(pos).astype(np.float64).reshape(-1, 3)
+    nsub = np.asarray(nsub, dtype=np.int64).reshape(3)
+    lo, hi = np.asarray(lo, dtype=np.float64).reshape(3), np.asarray(hi, dtype=np.float64).reshape(3)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        i = np.floor((x - lo) / ((hi - lo) / nsub.astype(np.float64)))
+    i = np.minimum(np.where(i >= 0.0, i, 0.0), (nsub - 1).astype(np.float64)).astype(np.int64)
+    return ((i[:, 0] * nsub[1] + i[:, 1]) * nsub[2] + i[:, 2]).astype(np.int32)
+
+
+def jackknife_from_counts(c, n1, m1, nr, mr, n2=None, m2=None, estimator="Natural", do_auto=True, do_cross=True):
+    """xi of the full sample and its jackknife covariance from integer counts, on the host in fp64 (no GPU).
+
+    ``c``: term -> ``(counts, ends)`` under ``D1D1, D1D2, D2D2, D1R, D2R, RR`` (those the estimator and the flags need),
+    ``counts`` of shape B and ``ends`` of (n, *B) as ``device.tpcf_jackknife_counts`` returns them; ``n1, n2, nr`` the
+    sample sizes and ``m1, m2, mr`` the objects per region, (n,) each.  Region k left out: sizes ``N - m[k]``; ordered
+    auto pairs ``2 counts - ends[k]``; cross and data-random pairs ``(2 counts - ends[k]) / 2``; each xi_k by
+    ``_estimate`` as for the full sample.  ``cov = (n - 1) / n sum_k (xi_k - mean)(xi_k - mean)^T`` over all n regions,
+    empty ones included, mean the mean of the xi_k, xi flattened per bin.  Returns, in halotools' order, ``(xi, cov)``
+    for one sample, ``(xi_11, xi_12, xi_22, cov_11, cov_12, cov_22)`` for two, ``(xi_12, cov_12)`` with ``do_cross``
+    only and ``(xi_11, xi_22, cov_11, cov_22)`` with ``do_auto`` only; xi of shape B, cov (prod B, prod B)."""
+    _check_estimator(estimator)
+    if not (do_auto or do_cross):
+        raise ValueError("do_auto and do_cross are both False: nothing to compute")
+    two = n2 is not None
+    f64 = lambda a: np.asarray(a).astype(np.float64)
+    n = len(np.asarray(mr).reshape(-1))
+    left = {key: float(size) - f64(m).reshape(-1) for key, size, m in (("1", n1, m1), ("2", n2, m2), ("R", nr, mr))
+            if m is not None}
+    full = {"1": n1, "2": n2, "R": nr}
+
+    def ordered(term, k=None):
+        """Ordered pairs of a term, or None when it was not counted: auto terms 2 x unordered, the others as counted."""
+        if term not in c:
+            return None
+        counts, ends = f64(c[term][0]), c[term][1]
+        auto = term in ("D1D1", "D2D2", "RR")
+        if k is None:
+            return 2.0 * counts if auto else counts
+        loo = 2.0 * counts - f64(ends[k])
+        return loo if auto else loo / 2.0
+
+    def term(a, b):
+        dd, dr = ("D1D2" if a != b else f"D{a}D{a}"), f"D{a}R"
+        xi = _estimate(estimator, ordered(dd), ordered(dr), ordered("RR"), full[a], full[b], nr)
+        xik = np.stack([np.asarray(_estimate(estimator, ordered(dd, k), ordered(dr, k), ordered("RR", k), left[a][k],
+                                             left[b][k], left["R"][k])).reshape(-1) for k in range(n)])
+        with np.errstate(invalid="ignore"):
+            d = xik - xik.mean(axis=0)
+            return xi, (n - 1.0) / n * (d.T @ d)
+
+    if not two:
+        return term("1", "1")
+    out = {}
+    if do_auto:
+        out[11], out[22] = term("1", "1"), term("2", "2")
+    if do_cross:
+        out[12] = term("1", "2")
+    keys = [k for k in (11, 12, 22) if k in out]
+    if keys == [12]:
+        return out[12]
+    return tuple(out[k][0] for k in keys) + tuple(out[k][1] for k in keys)
+
+
+def tpcf_jackknife(sample1, randoms, rbins, Nsub=[5, 5, 5], sample2=None, period=None, do_auto: bool = True,
+                   do_cross: bool = True, estimator: str = "Natural", num_threads: int = 1, seed=None, mu_bins=None,
+                   los: int = 2, return_counts: bool = False):
+    """xi and its covariance matrix from leave-one-subvolume-out resampling, with halotools' ``tpcf_jackknife``
+    arguments; ``mu_bins`` / ``los`` give xi(s, mu) instead of xi(r).  Every pair count with all its leave-one-out
+    variants comes from ONE pass over the pairs (``device.tpcf_jackknife_counts``).
+
+    * **Regions**: ``Nsub`` (an int or three) boxes per axis over one volume shared by ``sample1``, ``sample2`` and
+      ``randoms``: ``[0, period]``, or with ``period=None`` their joint bounding box; the region of an object is
+      ``jackknife_tags``'.  ``randoms`` are required.
+    * **Weights** (halotools' rule, recalled from its source, not checked against the library): with region k left out
+      a pair weighs 1 when neither end lies in k, 1/2 when exactly one does, 0 when both do.
+    * **Endpoint identity** (checked against a brute-force weighted count in the tests): with ``ends[k, b]`` the number
+      of pair ends in region k over the pairs of bin b, the weighted ordered auto pairs are ``2 counts - ends[k]`` and
+      twice the weighted cross pairs likewise, exact integers; ``ends.sum(0) == 2 counts``.
+    * **Estimate** (``jackknife_from_counts``): sample sizes ``N - (objects tagged k)``, each xi_k by the estimator of
+      the module docstring, the returned xi the full-sample one, ``cov = (n - 1) / n sum_k (xi_k - mean)(xi_k -
+      mean)^T`` over all regions, empty ones included.  Which counts enter the cross term (``D1R`` only) and the
+      return order - ``(xi, cov)``; ``(xi_11, xi_12, xi_22, cov_11, cov_12, cov_22)``; ``(xi_12, cov_12)`` with
+      ``do_cross`` only; ``(xi_11, xi_22, cov_11, cov_22)`` with ``do_auto`` only - are recalled, not checked.
+    * ``return_counts`` appends a dict term -> ``(counts, ends)`` of the raw int64 arrays that were needed, under
+      ``D1D1, D1D2, D2D2, D1R, D2R, RR``.  ``num_threads`` and ``seed`` are accepted and ignored."""
+    from ... import device as dev
+
+    _check_estimator(estimator)
+    if not (do_auto or do_cross):
+        raise ValueError("do_auto and do_cross are both False: nothing to compute")
+    if randoms is None:
+        raise ValueError("tpcf_jackknife needs randoms")
+    s, mu = dev.check_tpcf_edges(rbins, mu_bins, period, periodic=period is not None)
+    host = lambda a: dev.to_numpy(a) if hasattr(a, "is_cuda") else np.asarray(a)
+    sets = {"1": host(sample1), "R": host(randoms)}
+    if sample2 is not None:
+        sets["2"] = host(sample2)
+    nbins = (len(s) - 1) * (1 if mu is None else len(mu) - 1)
+    for p in sets.values():
+        nsub3, ntot, lo, hi = dev.check_jackknife_args(Nsub, np.shape(p), boxsize=period, nbins=nbins)
+    if lo is None:
+        filled = [p.astype(np.float64) for p in sets.values() if len(p)]
+        lo = np.min([p.min(axis=0) for p in filled], axis=0) if filled else np.zeros(3)
+        hi = np.max([p.max(axis=0) for p in filled], axis=0) if filled else np.zeros(3)
+    tags = {k: jackknife_tags(p, nsub3, lo, hi) for k, p in sets.items()}
+    m = {k: np.bincount(t, minlength=ntot) for k, t in tags.items()}
+
+    def count(a, b=None):
+        out = dev.tpcf_jackknife_counts(sets[a], ntot, s, mu, pos2=None if b is None else sets[b], boxsize=period,
+                                        los=los, tags1=tags[a], tags2=None if b is None else tags[b])
+        return tuple(dev.to_numpy(x) for x in out)
+
+    two = sample2 is not None
+    auto1, auto2, cross = do_auto or not two, do_auto and two, do_cross and two
+    c = {}
+    if auto1:
+        c["D1D1"] = count("1")
+    if cross:
+        c["D1D2"] = count("1", "2")
+    if auto2:
+        c["D2D2"] = count("2")
+    if estimator in _USES_DR:
+        c["D1R"] = count("1", "R")
+        if auto2:
+            c["D2R"] = count("2", "R")
+    if estimator in _USES_RR:
+        c["RR"] = count("R")
+    out = jackknife_from_counts(c, len(sets["1"]), m["1"], len(sets["R"]), m["R"], len(sets["2"]) if two else None,
+                                m.get("2"), estimator, do_auto, do_cross)
+    return out + (c,) if return_counts else out
 
 
 def tpcf_multipole(xi_s_mu, mu_bins, order: int = 0):

@@ -959,6 +959,39 @@ int ast_tpcf_cross_counts(void* work_d, size_t work_bytes, size_t n1, size_t n2,
                           int los, const double* s_edges_d, int ns, const double* mu_edges_d, int nmu,
                           int single_cell, unsigned long long* counts_d, void* stream);
 
+/* The pair counts of ast_tpcf_cross_counts together with what a leave-one-region-out jackknife needs (halotools'
+ * tpcf_jackknife: a pair weighs 1 when neither end lies in the left-out region k, 1/2 when one does, 0 when both do):
+ * every object carries a region tag in [0, nsub), and ends_d[k * nbins + b] is the number of pair ends in region k
+ * over the counted pairs of bin b (a pair with both ends in k adds 2).  Then, as exact integers, the ordered auto
+ * pairs (or twice the cross pairs) with region k left out are 2 counts[b] - ends[k][b], and sum_k ends[k][b] =
+ * 2 counts[b].  Two calls on one workspace of ast_tpcf_jk_workspace_bytes(n1, n2, ns, nmu, nsub) bytes (0 for bins
+ * that ast_tpcf_workspace_bytes refuses, nsub < 1 or nsub * nbins > ast_tpcf_jk_max_table()):
+ *
+ * ast_tpcf_jk_prepare: ast_tpcf_cross_prepare (shift, wrap, fp64 records, bounds_d[0..11]) plus the tag of every
+ * object.  tagsN_d != NULL: int32 per object, copied; a value outside [0, nsub[0] nsub[1] nsub[2]) sets
+ * bounds_d[12] = 1 (else 0) and is stored as region 0, so it is never an index past the table: the caller checks
+ * bounds_d[12] before counting.  tagsN_d == NULL: from the SHIFTED position, i_a = floor((x_a - lo_a) / dl_a) with
+ * dl_a = (hi_a - lo_a) / nsub_a (fp64, true divisions), clamped to [0, nsub_a - 1] on both sides (x = hi, a point
+ * outside the volume and a NaN belong to a border region), tag = (i_x nsub_y + i_y) nsub_z + i_z.  nsub, lo, hi:
+ * HOST pointers to 3 values each, nsub_a >= 1, lo / hi finite with hi_a >= lo_a.  bounds_d: 13 doubles.
+ *
+ * ast_tpcf_jk_counts: counts_d[nbins] as ast_tpcf_cross_counts (auto_pairs, boxsize, los, edges, bins and
+ * single_cell as there) and ends_d[nsub * nbins], both written, not accumulated, and zero when there is no pair.  nsub
+ * is the number of regions of the prepare call (a larger tag counts in the last region).  The table is counted in
+ * 32-bit LDS counters while nsub * nbins <= ast_tpcf_jk_lds_table(ns, nmu) and force_global == 0, flushed into ends_d
+ * with 64-bit integer atomics; else with 64-bit global atomics per pair end.  Integer sums: the same result either
+ * way and from call to call. */
+size_t ast_tpcf_jk_workspace_bytes(size_t n1, size_t n2, int ns, int nmu, int nsub);
+int ast_tpcf_jk_max_table(void);
+int ast_tpcf_jk_lds_table(int ns, int nmu);
+int ast_tpcf_jk_prepare(const void* pos1_d, int pos1_dtype, const void* vel1_d, int vel1_dtype, const int* tags1_d,
+                        size_t n1, const void* pos2_d, int pos2_dtype, const void* vel2_d, int vel2_dtype,
+                        const int* tags2_d, size_t n2, int los, double boxsize, const int* nsub, const double* lo,
+                        const double* hi, void* work_d, size_t work_bytes, double* bounds_d, void* stream);
+int ast_tpcf_jk_counts(void* work_d, size_t work_bytes, size_t n1, size_t n2, int auto_pairs, double boxsize, int los,
+                       const double* s_edges_d, int ns, const double* mu_edges_d, int nmu, int nsub, int single_cell,
+                       int force_global, unsigned long long* counts_d, unsigned long long* ends_d, void* stream);
+
 /* ------------------------------------------------- pairwise-velocity moments of one or two samples in a box */
 
 /* Count, sum v and sum v^2 per separation bin of the pairwise velocity of one or two samples, in a periodic cube or
