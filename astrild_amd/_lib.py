@@ -184,6 +184,9 @@ SIGNATURES = {
     "ast_tpcf_jk_prepare": (_i, [_vp, _i, _vp, _i, _vp, _sz, _vp, _i, _vp, _i, _vp, _sz, _i, _d, _vp, _vp, _vp, _vp, _sz,
                                  _vp, _vp]),
     "ast_tpcf_jk_counts": (_i, [_vp, _sz, _sz, _sz, _i, _d, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "ast_rppi_pair_counts": (_i, [_vp, _sz, _sz, _d, _i, _vp, _i, _vp, _i, _i, _i, _vp, _vp]),
+    "ast_rppi_cross_counts": (_i, [_vp, _sz, _sz, _sz, _i, _d, _i, _vp, _i, _vp, _i, _i, _i, _vp, _vp]),
+    "ast_rppi_jk_counts": (_i, [_vp, _sz, _sz, _sz, _i, _d, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "ast_pairvel_workspace_bytes": (_sz, [_sz, _sz, _i]),
     "ast_pairvel_max_bins": (_i, []),
     "ast_pairvel_prepare": (_i, [_vp, _i, _vp, _i, _sz, _vp, _i, _vp, _i, _sz, _vp, _sz, _vp, _vp]),

@@ -3,6 +3,7 @@
 //   bounds     GridBounds (order-preserving keys), grid_bounds_reset, grid_bounds_commit (the workgroup tail of every
 //              prep kernel) and grid_bounds_kernel (the box of one set, or of two and their union, to the caller);
 //   plan       grid_box_plan over a bounding box, grid_periodic_plan over a periodic cube, grid_plan choosing by boxsize;
+//              grid_cyl_plan, either of them with a reach per axis, for a cylinder along a line of sight;
 //   sort       grid_sort_set: clear, grid_box_count_kernel, grid_scan_kernel, grid_scatter_kernel;
 //   workspace  GridLayout, the one layout of a pair finder's scratch memory for one or two sets;
 //   host       grid_prepare, grid_sort_sets and GridSorted: a pair finder's entry points around its own kernels;
@@ -206,6 +207,66 @@ __global__ void grid_edge_plan_kernel(Params* prm, const double* __restrict__ ed
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     const double top = edges[nb];
     grid_plan(prm, pi_max > 0.0 ? sqrt(top * top + pi_max * pi_max) : top, boxsize, cap, single);
+}
+
+// The grid of a cylinder search, planned by one thread: pairs within rp_top across and pi_max along axis `los`, so
+// the reach of an axis is pi_max on `los` and rp_top on the other two, and every axis gets cells of its own width.
+// boxsize > 0, the periodic cube: floor(L / (reach_c (1 + 1e-6))) cells on axis c, at most 1024; an axis that would
+// get fewer than 3 gets exactly 1 (the walk skips its +-1 offsets, as for the one cell of a periodic plan, and the
+// minimum image of the pair arithmetic does the rest); while the grid exceeds `cap`, both reaches times 1.25.
+// boxsize == 0: grid_box_plan's rule over prm->box with the reach of each axis, its amax 1e-12 margin and its 1.25
+// growth (of every axis' width) until the grid fits `cap`.  single != 0, or a reach that is not positive (which no
+// growth would change): one cell.
+__device__ inline void grid_cyl_plan(GridBoxParams* prm, double rp_top, double pi_max, int los, double boxsize,
+                                     unsigned cap, int single) {
+    double reach[3], lo[3] = {0.0, 0.0, 0.0}, ext[3] = {boxsize, boxsize, boxsize};
+    for (int a = 0; a < 3; ++a) reach[a] = (a == los ? pi_max : rp_top) * (1.0 + 1e-6);
+    const bool periodic = boxsize > 0.0;
+    if (!periodic) {
+        double amax = 0.0;
+        for (int a = 0; a < 3; ++a) {
+            lo[a] = key2d(prm->box.kmin[a]);
+            const double hi = key2d(prm->box.kmax[a]);
+            ext[a] = hi - lo[a];
+            amax = fmax(amax, fmax(fabs(lo[a]), fabs(hi)));
+        }
+        for (int a = 0; a < 3; ++a) reach[a] += amax * 1e-12;
+    }
+    int dims[3] = {1, 1, 1};
+    if (!single && reach[0] > 0.0 && reach[1] > 0.0 && reach[2] > 0.0) {
+        for (;;) {
+            double prod = 1.0;
+            for (int a = 0; a < 3; ++a) {
+                double m = floor(ext[a] / reach[a]);
+                if (periodic) m = m >= 3.0 ? (m > 1024.0 ? 1024.0 : m) : 1.0;
+                else m = !(m >= 1.0) ? 1.0 : (m > (double)GRID_MAX_CELLS ? (double)GRID_MAX_CELLS : m);
+                dims[a] = (int)m;
+                prod *= m;
+            }
+            if (prod <= (double)cap) break;
+            for (int a = 0; a < 3; ++a) reach[a] *= 1.25;
+        }
+    }
+    for (int a = 0; a < 3; ++a) {
+        prm->lo[a] = lo[a];
+        prm->dims[a] = dims[a];
+        prm->inv_cs[a] = dims[a] > 1 ? (double)dims[a] / ext[a] : 0.0;
+    }
+    prm->ncells = (unsigned)dims[0] * (unsigned)dims[1] * (unsigned)dims[2];
+}
+
+// For a cylinder whose reaches are in device memory: the top edges rp_edges[nrp] and pi_edges[npi].  iso == 0: the
+// plan above; iso != 0: the isotropic plan that grid_edge_plan_kernel makes for pi_max = pi_edges[npi], cells of
+// sqrt(rp_top^2 + pi_max^2) on every axis.
+template <typename Params>
+__global__ void grid_cyl_plan_kernel(Params* prm, const double* __restrict__ rp_edges, int nrp,
+                                     const double* __restrict__ pi_edges, int npi, int los, double boxsize,
+                                     unsigned cap, int single, int iso) {
+    static_assert(std::is_same<Params, GridBoxParams>::value, "grid_cyl_plan_kernel plans a GridBoxParams");
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const double top = rp_edges[nrp], pi_max = pi_edges[npi];
+    if (iso) grid_plan(prm, sqrt(top * top + pi_max * pi_max), boxsize, cap, single);
+    else grid_cyl_plan(prm, top, pi_max, los, boxsize, cap, single);
 }
 
 // ---- sort: objects ordered by cell with a counting sort

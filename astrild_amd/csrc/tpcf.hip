@@ -2,7 +2,8 @@
 // box, or of two samples in a periodic box or with open boundaries: per-object prep (redshift-space shift, wrap,
 // bounds), the uniform cell grid of cell_grid.h (counting sort by cell) as the pair finder, a tiled pair kernel that
 // counts minimum-image pairs into an exact integer (s, mu) histogram in LDS, and a fixed-order sum of the workgroup
-// rows.  For jackknife errors (ast_tpcf_jk_*) every object also carries a region tag, and the same walk counts the pair
+// rows.  The same kernels, compiled for another pair geometry, count (r_p, pi) bins across and along the line of sight
+// (ast_rppi_*: halotools' rp_pi_tpcf / wp), on a grid planned with a reach per axis.  For jackknife errors (ast_tpcf_jk_*) every object also carries a region tag, and the same walk counts the pair
 // ends per (region, bin) instead, from which all leave-one-region-out counts follow as integers.  All pair arithmetic
 // is fp64 (the library is built with -ffp-contract=off).
 #include "ast_common.h"
@@ -164,12 +165,74 @@ __device__ __forceinline__ int tp_pair_bin(const double (&ri)[3], double xj, dou
     return lo * nmu + ml;
 }
 
+// The geometry of a pair kernel, a compile-time parameter: (s, mu) bins of tp_pair_bin, or (r_p, pi) bins of
+// tp_rppi_bin (ast_rppi_*), where TpBins' s_edges / ns are the r_p edges and mu_edges / nmu (> 0) the pi edges.
+enum TpGeom { TP_SMU = 0, TP_RPPI = 1 };
+
+// The axes a < b other than los.
+__device__ __forceinline__ int tp_axis_a(int los) { return los == 0 ? 1 : 0; }
+__device__ __forceinline__ int tp_axis_b(int los) { return los == 2 ? 1 : 2; }
+
+// The (r_p, pi) bin of one pair, or -1 when it counts nowhere.  Both objects come with their axes in the order
+// (a, b, los), a < b the axes other than the line of sight (the kernels permute on load).  p_c = |x_i - x_j| per axis,
+// periodic: p_c = min(p_c, L - p_c), tp_pair_bin's arithmetic; rp2 = p_a p_a + p_b p_b (the operand order of
+// pair_velocity.hip's AST_PAIRVEL_LOS) and pi = p_los.  A pair counts in bin (k, l) when s2[k] < rp2 <= s2[k + 1] and
+// me[l] < pi <= me[l + 1]: s2 the nrp + 1 squared r_p edges, me the npi + 1 pi edges as given, both in LDS, both
+// bins by binary search on fp64 comparisons.
+__device__ __forceinline__ int tp_rppi_bin(const double (&ri)[3], double aj, double bj, double lj, bool periodic,
+                                           double boxsize, const double* s2, int nrp, const double* me, int npi,
+                                           const TpRange& rg) {
+    double pa = fabs(ri[0] - aj), pb = fabs(ri[1] - bj), pl = fabs(ri[2] - lj);
+    if (periodic) {
+        pa = fmin(pa, boxsize - pa);
+        pb = fmin(pb, boxsize - pb);
+        pl = fmin(pl, boxsize - pl);
+    }
+    const double rp2 = pa * pa + pb * pb;
+    if (!(rp2 <= rg.s2hi) || !(rp2 > rg.s2lo) || !(pl <= rg.muhi) || !(pl > rg.mulo)) return -1;
+    int lo = 0, hi = nrp;                               // s2[lo] < rp2 <= s2[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (rp2 <= s2[mid]) hi = mid; else lo = mid;
+    }
+    int ml = 0, mh = npi;                               // me[ml] < pl <= me[mh]
+    while (mh - ml > 1) {
+        const int mid = (ml + mh) >> 1;
+        if (pl <= me[mid]) mh = mid; else ml = mid;
+    }
+    return lo * npi + ml;
+}
+
+// The bin of the pair (i, staged j in slot q) in the geometry GEOM; for TP_RPPI ri and the stage hold (a, b, los).
+template <int GEOM>
+__device__ __forceinline__ int tp_bin_of(const double (&ri)[3], const double* jr, int q, bool periodic, double boxsize,
+                                         int los, const double* s2, int ns, const double* me, int nmu,
+                                         const TpRange& rg) {
+    if (GEOM == TP_RPPI)
+        return tp_rppi_bin(ri, jr[q], jr[TP_BLOCK + q], jr[2 * TP_BLOCK + q], periodic, boxsize, s2, ns, me, nmu, rg);
+    return tp_pair_bin(ri, jr[q], jr[TP_BLOCK + q], jr[2 * TP_BLOCK + q], periodic, boxsize, los, s2, ns, me, nmu, rg);
+}
+
+// A record's position as a pair kernel of geometry GEOM holds it: as stored, or for TP_RPPI in the order (a, b, los).
+template <int GEOM>
+__device__ __forceinline__ void tp_axes(const double (&r)[3], int los, double (&out)[3]) {
+    if (GEOM == TP_RPPI) {
+        const int la = tp_axis_a(los), lb = tp_axis_b(los);
+        out[0] = la == 0 ? r[0] : r[1];
+        out[1] = lb == 1 ? r[1] : r[2];
+        out[2] = los == 0 ? r[0] : (los == 1 ? r[1] : r[2]);
+    } else {
+        for (int c = 0; c < 3; ++c) out[c] = r[c];
+    }
+}
+
 // The walk of cell_grid.h (grid_pair_walk) with the positions of the staged j objects in LDS; `periodic` and
-// `auto_pairs` as there; the bin of a pair is tp_pair_bin's.
+// `auto_pairs` as there; the bin of a pair is tp_pair_bin's, or tp_rppi_bin's for GEOM = TP_RPPI.
 // Each pair adds 1 to a 32-bit LDS counter of the wave's histogram copy (hcopies copies, wave w uses w % hcopies).
 // Before an LDS stage that could take a counter past flush_at pairs since the last flush, the workgroup adds its
 // counters into its own 64-bit row of part (plain loads and stores: no other workgroup touches the row) and clears
 // them; the row is complete after the final flush.  No global atomics.
+template <int GEOM>
 __device__ __forceinline__ void tp_count_pairs(const TpObj* __restrict__ sorted1, const unsigned* __restrict__ cell_start1,
                                                const unsigned* __restrict__ tile_start,
                                                const TpObj* __restrict__ sorted2,
@@ -210,19 +273,19 @@ __device__ __forceinline__ void tp_count_pairs(const TpObj* __restrict__ sorted1
     TpObj oi;
     grid_pair_walk<TP_BLOCK>(
         cell_start1, tile_start, cell_start2, prm, periodic, auto_pairs,
-        [&](unsigned i) { oi = sorted1[i]; },
+        [&](unsigned i) { tp_axes<GEOM>(sorted1[i].r, los, oi.r); },
         [&](unsigned ni, int m) {
             const unsigned long long stage = (unsigned long long)ni * (unsigned long long)m;
             if (pending + stage > bn.flush_at) flush();
             pending += stage;
         },
         [&](unsigned j, int t) {
-            const TpObj oj = sorted2[j];
+            TpObj oj;
+            tp_axes<GEOM>(sorted2[j].r, los, oj.r);
             for (int c = 0; c < 3; ++c) jr[c * TP_BLOCK + t] = oj.r[c];
         },
         [&](int q) {
-            const int bin = tp_pair_bin(oi.r, jr[q], jr[TP_BLOCK + q], jr[2 * TP_BLOCK + q], periodic, boxsize, los, s2,
-                                        ns, me, nmu, rg);
+            const int bin = tp_bin_of<GEOM>(oi.r, jr, q, periodic, boxsize, los, s2, ns, me, nmu, rg);
             if (bin < 0) return;
             atomicAdd(&whist[bin], 1u);
         });
@@ -230,21 +293,23 @@ __device__ __forceinline__ void tp_count_pairs(const TpObj* __restrict__ sorted1
 }
 
 // One set in a periodic box: the topology is known when the kernel is compiled.
+template <int GEOM>
 __global__ void __launch_bounds__(TP_BLOCK)
 tp_pair_kernel(const TpObj* __restrict__ sorted, const unsigned* __restrict__ cell_start,
                const unsigned* __restrict__ tile_start, const GridBoxParams* prm, TpBins bn,
                unsigned long long* __restrict__ part) {
-    tp_count_pairs(sorted, cell_start, tile_start, sorted, cell_start, prm, true, true, bn, part);
+    tp_count_pairs<GEOM>(sorted, cell_start, tile_start, sorted, cell_start, prm, true, true, bn, part);
 }
 
 // Two sets (auto_pairs != 0: sorted2 / cell_start2 are set 1's own), periodic when bn.boxsize > 0.
+template <int GEOM>
 __global__ void __launch_bounds__(TP_BLOCK)
 tpx_pair_kernel(const TpObj* __restrict__ sorted1, const unsigned* __restrict__ cell_start1,
                 const unsigned* __restrict__ tile_start, const TpObj* __restrict__ sorted2,
                 const unsigned* __restrict__ cell_start2, const GridBoxParams* prm, int auto_pairs, TpBins bn,
                 unsigned long long* __restrict__ part) {
-    tp_count_pairs(sorted1, cell_start1, tile_start, sorted2, cell_start2, prm, bn.boxsize > 0.0, auto_pairs != 0, bn,
-                   part);
+    tp_count_pairs<GEOM>(sorted1, cell_start1, tile_start, sorted2, cell_start2, prm, bn.boxsize > 0.0, auto_pairs != 0,
+                         bn, part);
 }
 
 // counts[bin] = sum of the TP_GRID workgroup rows, in row order.
@@ -264,7 +329,7 @@ tp_reduce_kernel(const unsigned long long* __restrict__ part, int nbins, unsigne
 // with one global atomicAdd per non-zero counter before a stage that could take a counter past flush_at (a pair adds
 // up to 2 to one counter: 2 ni m per stage) and at the end; integer sums, so the order does not matter.  !LDS (the
 // table does not fit): 64-bit global atomics straight into `ends`.
-template <bool LDS>
+template <bool LDS, int GEOM>
 __global__ void __launch_bounds__(TP_BLOCK)
 tj_pair_kernel(const TjObj* __restrict__ sorted1, const unsigned* __restrict__ cell_start1,
                const unsigned* __restrict__ tile_start, const TjObj* __restrict__ sorted2,
@@ -306,7 +371,11 @@ tj_pair_kernel(const TjObj* __restrict__ sorted1, const unsigned* __restrict__ c
     unsigned ti = 0;                                    // tag * nbins of the thread's i
     grid_pair_walk<TP_BLOCK>(
         cell_start1, tile_start, cell_start2, prm, periodic, auto_pairs != 0,
-        [&](unsigned i) { oi = sorted1[i]; ti = min(oi.tag, tmax) * nbins; },
+        [&](unsigned i) {
+            const TjObj o = sorted1[i];
+            tp_axes<GEOM>(o.r, los, oi.r);
+            ti = min(o.tag, tmax) * nbins;
+        },
         [&](unsigned ni, int m) {
             if (!LDS) return;
             const unsigned long long stage = 2ull * (unsigned long long)ni * (unsigned long long)m;
@@ -315,12 +384,13 @@ tj_pair_kernel(const TjObj* __restrict__ sorted1, const unsigned* __restrict__ c
         },
         [&](unsigned j, int t) {
             const TjObj oj = sorted2[j];
-            for (int c = 0; c < 3; ++c) jr[c * TP_BLOCK + t] = oj.r[c];
+            double rj[3];
+            tp_axes<GEOM>(oj.r, los, rj);
+            for (int c = 0; c < 3; ++c) jr[c * TP_BLOCK + t] = rj[c];
             jt[t] = min(oj.tag, tmax) * nbins;
         },
         [&](int q) {
-            const int bin = tp_pair_bin(oi.r, jr[q], jr[TP_BLOCK + q], jr[2 * TP_BLOCK + q], periodic, boxsize, los, s2,
-                                        ns, me, nmu, rg);
+            const int bin = tp_bin_of<GEOM>(oi.r, jr, q, periodic, boxsize, los, s2, ns, me, nmu, rg);
             if (bin < 0) return;
             const unsigned ei = ti + (unsigned)bin, ej = jt[q] + (unsigned)bin;
             if (LDS) {
@@ -380,34 +450,53 @@ TpBins tp_bins(double boxsize, int los, const double* s_edges, int ns, const dou
     return TpBins{boxsize, los, s_edges, ns, mu_edges, nmu, hcopies, flush_at};
 }
 
-// The pair counts of a prepared workspace with pairs in it: the plan for the top s edge, the sort, the pair kernel -
-// tp_pair_kernel for the one set of ast_tpcf_* (`cross` false), else tpx_pair_kernel - and the reduce.
-int tp_counts(bool cross, char* ws, const GridLayout& L, const size_t* n, int auto_pairs, double boxsize, int los,
-              const double* s_edges_d, int ns, const double* mu_edges_d, int nmu, int single_cell,
-              unsigned long long* counts_d, hipStream_t s) {
+// The plan of a call's grid, by one thread.  TP_SMU: cells of the top s edge.  TP_RPPI (s / mu edges: the r_p / pi
+// edges): the cylinder's own plan, or with `iso` the isotropic one for sqrt(rp_top^2 + pi_max^2).
+int tp_plan(int geom, int iso, GridBoxParams* prm, const GridLayout& L, double boxsize, int los, const double* s_edges_d,
+            int ns, const double* mu_edges_d, int nmu, int single_cell, hipStream_t s) {
+    if (geom == TP_RPPI)
+        grid_cyl_plan_kernel<<<1, 64, 0, s>>>(prm, s_edges_d, ns, mu_edges_d, nmu, los, boxsize, (unsigned)L.cap,
+                                              single_cell, iso);
+    else
+        grid_edge_plan_kernel<<<1, 64, 0, s>>>(prm, s_edges_d, ns, 0.0, boxsize, (unsigned)L.cap, single_cell);
+    AST_CHECK_LAUNCH();
+    return AST_OK;
+}
+
+// The pair counts of a prepared workspace with pairs in it: the plan for the top s edge (tp_plan), the sort, the pair
+// kernel - tp_pair_kernel for the one set of ast_tpcf_* (`cross` false), else tpx_pair_kernel - and the reduce.
+// geom: TP_SMU, or TP_RPPI with `iso` choosing its plan.
+int tp_counts(int geom, int iso, bool cross, char* ws, const GridLayout& L, const size_t* n, int auto_pairs,
+              double boxsize, int los, const double* s_edges_d, int ns, const double* mu_edges_d, int nmu,
+              int single_cell, unsigned long long* counts_d, hipStream_t s) {
     const int nbins = nbins_of(ns, nmu);
     const int q2 = cross && !auto_pairs ? 1 : 0;
+    const bool rppi = geom == TP_RPPI;
     const GridSorted<TpObj, unsigned long long> g(ws, L, q2);
     {
-        AST_PROF(cross ? "tpcf_cross_grid" : "tpcf_grid", s);
-        grid_edge_plan_kernel<<<1, 64, 0, s>>>(g.prm, s_edges_d, ns, 0.0, boxsize, (unsigned)L.cap, single_cell);
-        AST_CHECK_LAUNCH();
+        AST_PROF(rppi ? (cross ? "rppi_cross_grid" : "rppi_grid") : (cross ? "tpcf_cross_grid" : "tpcf_grid"), s);
+        if (int rc = tp_plan(geom, iso, g.prm, L, boxsize, los, s_edges_d, ns, mu_edges_d, nmu, single_cell, s))
+            return rc;
         if (int rc = grid_sort_sets<TP_BLOCK, TpObj>(ws, L, q2, n, s)) return rc;
     }
     size_t lds;
     const TpBins bn = tp_bins(boxsize, los, s_edges_d, ns, mu_edges_d, nmu, &lds);
     AST_CHECK_ARG(lds <= TP_LDS);
     {
-        AST_PROF(cross ? "tpcf_cross_pairs" : "tpcf_pairs", s);
-        if (cross)
-            tpx_pair_kernel<<<TP_GRID, TP_BLOCK, lds, s>>>(g.sorted1, g.cell_start1, g.tile_start1, g.sorted2,
-                                                           g.cell_start2, g.prm, auto_pairs, bn, g.part);
-        else
-            tp_pair_kernel<<<TP_GRID, TP_BLOCK, lds, s>>>(g.sorted1, g.cell_start1, g.tile_start1, g.prm, bn, g.part);
+        AST_PROF(rppi ? (cross ? "rppi_cross_pairs" : "rppi_pairs") : (cross ? "tpcf_cross_pairs" : "tpcf_pairs"), s);
+        if (cross) {
+            const auto pairs = rppi ? tpx_pair_kernel<TP_RPPI> : tpx_pair_kernel<TP_SMU>;
+            pairs<<<TP_GRID, TP_BLOCK, lds, s>>>(g.sorted1, g.cell_start1, g.tile_start1, g.sorted2, g.cell_start2,
+                                                 g.prm, auto_pairs, bn, g.part);
+        } else {
+            const auto pairs = rppi ? tp_pair_kernel<TP_RPPI> : tp_pair_kernel<TP_SMU>;
+            pairs<<<TP_GRID, TP_BLOCK, lds, s>>>(g.sorted1, g.cell_start1, g.tile_start1, g.prm, bn, g.part);
+        }
         AST_CHECK_LAUNCH();
     }
     {
-        AST_PROF(cross ? "tpcf_cross_reduce" : "tpcf_reduce", s);
+        AST_PROF(rppi ? (cross ? "rppi_cross_reduce" : "rppi_reduce") : (cross ? "tpcf_cross_reduce" : "tpcf_reduce"),
+                 s);
         tp_reduce_kernel<<<(nbins + 255) / 256, 256, 0, s>>>(g.part, nbins, counts_d);
         AST_CHECK_LAUNCH();
     }
@@ -428,16 +517,17 @@ inline GridLayout tj_layout(size_t n1, size_t n2) {
 inline int tj_lds_table(int ns, int nmu) { return (int)((TJ_LDS - tp_fixed_lds(ns, nmu, 1)) / 4); }
 
 // tp_counts for the jackknife: the plan, the sort, the zeroed table, the pair kernel (LDS or global) and the counts.
-int tj_counts(char* ws, const GridLayout& L, const size_t* n, int auto_pairs, double boxsize, int los,
+int tj_counts(int geom, int iso, char* ws, const GridLayout& L, const size_t* n, int auto_pairs, double boxsize, int los,
               const double* s_edges_d, int ns, const double* mu_edges_d, int nmu, int nsub, int single_cell,
               int force_global, unsigned long long* counts_d, unsigned long long* ends_d, hipStream_t s) {
     const int nbins = nbins_of(ns, nmu), table = nsub * nbins;
     const int q2 = auto_pairs ? 0 : 1;
+    const bool rppi = geom == TP_RPPI;
     const GridSorted<TjObj, unsigned long long> g(ws, L, q2);
     {
-        AST_PROF("tpcf_jk_grid", s);
-        grid_edge_plan_kernel<<<1, 64, 0, s>>>(g.prm, s_edges_d, ns, 0.0, boxsize, (unsigned)L.cap, single_cell);
-        AST_CHECK_LAUNCH();
+        AST_PROF(rppi ? "rppi_jk_grid" : "tpcf_jk_grid", s);
+        if (int rc = tp_plan(geom, iso, g.prm, L, boxsize, los, s_edges_d, ns, mu_edges_d, nmu, single_cell, s))
+            return rc;
         if (int rc = grid_sort_sets<TP_BLOCK, TjObj>(ws, L, q2, n, s)) return rc;
     }
     const bool use_lds = !force_global && table <= tj_lds_table(ns, nmu);
@@ -447,20 +537,24 @@ int tj_counts(char* ws, const GridLayout& L, const size_t* n, int auto_pairs, do
     AST_CHECK_ARG(lds <= TJ_LDS);
     static ast::PerDeviceOnce attr_once;
     if (attr_once.need()) {
-        AST_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&tj_pair_kernel<true>),
+        AST_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&tj_pair_kernel<true, TP_SMU>),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)TJ_LDS));
+        AST_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&tj_pair_kernel<true, TP_RPPI>),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)TJ_LDS));
         attr_once.mark();
     }
     AST_CHECK_HIP(hipMemsetAsync(ends_d, 0, (size_t)table * sizeof(unsigned long long), s));
     {
-        AST_PROF(use_lds ? "tpcf_jk_pairs_lds" : "tpcf_jk_pairs_global", s);
-        const auto pairs = use_lds ? tj_pair_kernel<true> : tj_pair_kernel<false>;
+        AST_PROF(rppi ? (use_lds ? "rppi_jk_pairs_lds" : "rppi_jk_pairs_global")
+                      : (use_lds ? "tpcf_jk_pairs_lds" : "tpcf_jk_pairs_global"), s);
+        const auto pairs = rppi ? (use_lds ? tj_pair_kernel<true, TP_RPPI> : tj_pair_kernel<false, TP_RPPI>)
+                                : (use_lds ? tj_pair_kernel<true, TP_SMU> : tj_pair_kernel<false, TP_SMU>);
         pairs<<<TP_GRID, TP_BLOCK, lds, s>>>(g.sorted1, g.cell_start1, g.tile_start1, g.sorted2, g.cell_start2, g.prm,
                                              auto_pairs, bn, table, ends_d);
         AST_CHECK_LAUNCH();
     }
     {
-        AST_PROF("tpcf_jk_counts", s);
+        AST_PROF(rppi ? "rppi_jk_counts" : "tpcf_jk_counts", s);
         tj_counts_kernel<<<(nbins + 255) / 256, 256, 0, s>>>(ends_d, nsub, nbins, counts_d);
         AST_CHECK_LAUNCH();
     }
@@ -494,10 +588,13 @@ extern "C" int ast_tpcf_prepare(const void* pos_d, int pos_dtype, const void* ve
     });
 }
 
-extern "C" int ast_tpcf_pair_counts(void* work_d, size_t work_bytes, size_t n, double boxsize, int los,
-                                    const double* s_edges_d, int ns, const double* mu_edges_d, int nmu,
-                                    int single_cell, unsigned long long* counts_d, void* stream) {
+namespace {
+// The entry point of one set in a periodic box, for either geometry (TP_RPPI: nmu >= 1).
+int tp_pair_counts_entry(int geom, int iso, void* work_d, size_t work_bytes, size_t n, double boxsize, int los,
+                         const double* s_edges_d, int ns, const double* mu_edges_d, int nmu, int single_cell,
+                         unsigned long long* counts_d, void* stream) {
     AST_CHECK_ARG(bins_ok(ns, nmu));
+    AST_CHECK_ARG(geom == TP_SMU || nmu >= 1);
     AST_CHECK_ARG(los >= 0 && los <= 2);
     AST_CHECK_ARG(boxsize > 0.0 && std::isfinite(boxsize));
     AST_CHECK_ARG(grid_count_ok(n));
@@ -509,8 +606,24 @@ extern "C" int ast_tpcf_pair_counts(void* work_d, size_t work_bytes, size_t n, d
         AST_CHECK_HIP(hipMemsetAsync(counts_d, 0, nbins * sizeof(unsigned long long), s));
         return AST_OK;
     }
-    return tp_counts(false, (char*)work_d, tp_layout(1, n, 0, nbins), &n, 1, boxsize, los, s_edges_d, ns, mu_edges_d,
-                     nmu, single_cell, counts_d, s);
+    return tp_counts(geom, iso, false, (char*)work_d, tp_layout(1, n, 0, nbins), &n, 1, boxsize, los, s_edges_d, ns,
+                     mu_edges_d, nmu, single_cell, counts_d, s);
+}
+}  // namespace
+
+extern "C" int ast_tpcf_pair_counts(void* work_d, size_t work_bytes, size_t n, double boxsize, int los,
+                                    const double* s_edges_d, int ns, const double* mu_edges_d, int nmu,
+                                    int single_cell, unsigned long long* counts_d, void* stream) {
+    return tp_pair_counts_entry(TP_SMU, 0, work_d, work_bytes, n, boxsize, los, s_edges_d, ns, mu_edges_d, nmu,
+                                single_cell, counts_d, stream);
+}
+
+extern "C" int ast_rppi_pair_counts(void* work_d, size_t work_bytes, size_t n, double boxsize, int los,
+                                    const double* rp_edges_d, int nrp, const double* pi_edges_d, int npi,
+                                    int single_cell, int plan, unsigned long long* counts_d, void* stream) {
+    AST_CHECK_ARG(plan == 0 || plan == 1);
+    return tp_pair_counts_entry(TP_RPPI, plan, work_d, work_bytes, n, boxsize, los, rp_edges_d, nrp, pi_edges_d, npi,
+                                single_cell, counts_d, stream);
 }
 
 // ---- two sets, periodic cube or open boundaries
@@ -546,11 +659,13 @@ extern "C" int ast_tpcf_cross_prepare(const void* pos1_d, int pos1_dtype, const 
     });
 }
 
-extern "C" int ast_tpcf_cross_counts(void* work_d, size_t work_bytes, size_t n1, size_t n2, int auto_pairs,
-                                     double boxsize, int los, const double* s_edges_d, int ns,
-                                     const double* mu_edges_d, int nmu, int single_cell,
-                                     unsigned long long* counts_d, void* stream) {
+namespace {
+// The entry point of two sets, for either geometry (TP_RPPI: nmu >= 1).
+int tp_cross_counts_entry(int geom, int iso, void* work_d, size_t work_bytes, size_t n1, size_t n2, int auto_pairs,
+                          double boxsize, int los, const double* s_edges_d, int ns, const double* mu_edges_d, int nmu,
+                          int single_cell, unsigned long long* counts_d, void* stream) {
     AST_CHECK_ARG(bins_ok(ns, nmu));
+    AST_CHECK_ARG(geom == TP_SMU || nmu >= 1);
     AST_CHECK_ARG(los >= 0 && los <= 2);
     AST_CHECK_ARG(boxsize >= 0.0 && std::isfinite(boxsize));
     AST_CHECK_ARG(grid_count_ok(n1) && grid_count_ok(n2));
@@ -563,8 +678,26 @@ extern "C" int ast_tpcf_cross_counts(void* work_d, size_t work_bytes, size_t n1,
         return AST_OK;
     }
     const size_t n[2] = {n1, n2};
-    return tp_counts(true, (char*)work_d, tp_layout(2, n1, n2, nbins), n, auto_pairs, boxsize, los, s_edges_d, ns,
-                     mu_edges_d, nmu, single_cell, counts_d, s);
+    return tp_counts(geom, iso, true, (char*)work_d, tp_layout(2, n1, n2, nbins), n, auto_pairs, boxsize, los, s_edges_d,
+                     ns, mu_edges_d, nmu, single_cell, counts_d, s);
+}
+}  // namespace
+
+extern "C" int ast_tpcf_cross_counts(void* work_d, size_t work_bytes, size_t n1, size_t n2, int auto_pairs,
+                                     double boxsize, int los, const double* s_edges_d, int ns,
+                                     const double* mu_edges_d, int nmu, int single_cell,
+                                     unsigned long long* counts_d, void* stream) {
+    return tp_cross_counts_entry(TP_SMU, 0, work_d, work_bytes, n1, n2, auto_pairs, boxsize, los, s_edges_d, ns,
+                                 mu_edges_d, nmu, single_cell, counts_d, stream);
+}
+
+extern "C" int ast_rppi_cross_counts(void* work_d, size_t work_bytes, size_t n1, size_t n2, int auto_pairs,
+                                     double boxsize, int los, const double* rp_edges_d, int nrp,
+                                     const double* pi_edges_d, int npi, int single_cell, int plan,
+                                     unsigned long long* counts_d, void* stream) {
+    AST_CHECK_ARG(plan == 0 || plan == 1);
+    return tp_cross_counts_entry(TP_RPPI, plan, work_d, work_bytes, n1, n2, auto_pairs, boxsize, los, rp_edges_d, nrp,
+                                 pi_edges_d, npi, single_cell, counts_d, stream);
 }
 
 
@@ -622,11 +755,14 @@ extern "C" int ast_tpcf_jk_prepare(const void* pos1_d, int pos1_dtype, const voi
     });
 }
 
-extern "C" int ast_tpcf_jk_counts(void* work_d, size_t work_bytes, size_t n1, size_t n2, int auto_pairs,
-                                  double boxsize, int los, const double* s_edges_d, int ns, const double* mu_edges_d,
-                                  int nmu, int nsub, int single_cell, int force_global,
-                                  unsigned long long* counts_d, unsigned long long* ends_d, void* stream) {
+namespace {
+// The entry point of the jackknife counts, for either geometry (TP_RPPI: nmu >= 1).
+int tj_counts_entry(int geom, int iso, void* work_d, size_t work_bytes, size_t n1, size_t n2, int auto_pairs,
+                    double boxsize, int los, const double* s_edges_d, int ns, const double* mu_edges_d, int nmu,
+                    int nsub, int single_cell, int force_global, unsigned long long* counts_d, unsigned long long* ends_d,
+                    void* stream) {
     AST_CHECK_ARG(tj_ok(ns, nmu, nsub));
+    AST_CHECK_ARG(geom == TP_SMU || nmu >= 1);
     AST_CHECK_ARG(los >= 0 && los <= 2);
     AST_CHECK_ARG(boxsize >= 0.0 && std::isfinite(boxsize));
     AST_CHECK_ARG(grid_count_ok(n1) && grid_count_ok(n2));
@@ -640,6 +776,24 @@ extern "C" int ast_tpcf_jk_counts(void* work_d, size_t work_bytes, size_t n1, si
         return AST_OK;
     }
     const size_t n[2] = {n1, n2};
-    return tj_counts((char*)work_d, tj_layout(n1, n2), n, auto_pairs, boxsize, los, s_edges_d, ns, mu_edges_d, nmu, nsub,
-                     single_cell, force_global, counts_d, ends_d, s);
+    return tj_counts(geom, iso, (char*)work_d, tj_layout(n1, n2), n, auto_pairs, boxsize, los, s_edges_d, ns, mu_edges_d,
+                     nmu, nsub, single_cell, force_global, counts_d, ends_d, s);
+}
+}  // namespace
+
+extern "C" int ast_tpcf_jk_counts(void* work_d, size_t work_bytes, size_t n1, size_t n2, int auto_pairs,
+                                  double boxsize, int los, const double* s_edges_d, int ns, const double* mu_edges_d,
+                                  int nmu, int nsub, int single_cell, int force_global,
+                                  unsigned long long* counts_d, unsigned long long* ends_d, void* stream) {
+    return tj_counts_entry(TP_SMU, 0, work_d, work_bytes, n1, n2, auto_pairs, boxsize, los, s_edges_d, ns, mu_edges_d,
+                           nmu, nsub, single_cell, force_global, counts_d, ends_d, stream);
+}
+
+extern "C" int ast_rppi_jk_counts(void* work_d, size_t work_bytes, size_t n1, size_t n2, int auto_pairs,
+                                  double boxsize, int los, const double* rp_edges_d, int nrp, const double* pi_edges_d,
+                                  int npi, int nsub, int single_cell, int force_global, int plan,
+                                  unsigned long long* counts_d, unsigned long long* ends_d, void* stream) {
+    AST_CHECK_ARG(plan == 0 || plan == 1);
+    return tj_counts_entry(TP_RPPI, plan, work_d, work_bytes, n1, n2, auto_pairs, boxsize, los, rp_edges_d, nrp,
+                           pi_edges_d, npi, nsub, single_cell, force_global, counts_d, ends_d, stream);
 }

@@ -1548,10 +1548,16 @@ def tpcf_pair_counts(pos, boxsize, s_edges, mu_edges=None, vel=None, los=2):
     return _tpcf_counts([one], None, s, mu, float(boxsize), True, los)
 
 
-def _tpcf_counts(sets, auto, s, mu, box, periodic, los):
+def _rppi_plan():
+    """The ``plan`` argument of ast_rppi_*: 0, cells of a width per axis; with ASTRILD_RPPI_ANISO=0 the isotropic 1."""
+    return 1 if os.environ.get("ASTRILD_RPPI_ANISO", "1") == "0" else 0
+
+
+def _tpcf_counts(sets, auto, s, mu, box, periodic, los, rppi=False):
     """The calls of tpcf_pair_counts (``sets``: its one ``_pair_sample``; ast_tpcf_prepare / ast_tpcf_pair_counts) and
     of tpcf_cross_counts (two, the second (None, None, 0) for ``auto``; ast_tpcf_cross_prepare / ast_tpcf_cross_counts),
-    with the check of the device bounds between the two."""
+    with the check of the device bounds between the two.  ``rppi``: ``s`` / ``mu`` are r_p / pi edges and the counts
+    are ast_rppi_pair_counts' / ast_rppi_cross_counts', on the same prepared workspace."""
     lib = _lib.lib()
     cross = len(sets) == 2
     sizes = [n for _, _, n in sets]
@@ -1575,12 +1581,16 @@ def _tpcf_counts(sets, auto, s, mu, box, periodic, los):
     s_d = as_device(s)
     mu_d = as_device(mu) if mu is not None else None
     counts = torch.empty((ns, nmu) if nmu else (ns,), dtype=torch.int64, device=device_)
+    tail = (int(single), _rppi_plan()) if rppi else (int(single),)
     if cross:
-        check(lib.ast_tpcf_cross_counts(ptr(work), ws_bytes, n1, n2, int(auto), box, los, ptr(s_d), ns, ptr(mu_d), nmu,
-                                        int(single), ptr(counts), st), "ast_tpcf_cross_counts")
+        count, name = (lib.ast_rppi_cross_counts, "ast_rppi_cross_counts") if rppi else \
+            (lib.ast_tpcf_cross_counts, "ast_tpcf_cross_counts")
+        check(count(ptr(work), ws_bytes, n1, n2, int(auto), box, los, ptr(s_d), ns, ptr(mu_d), nmu, *tail, ptr(counts),
+                    st), name)
     else:
-        check(lib.ast_tpcf_pair_counts(ptr(work), ws_bytes, n, box, los, ptr(s_d), ns, ptr(mu_d), nmu, int(single),
-                                       ptr(counts), st), "ast_tpcf_pair_counts")
+        count, name = (lib.ast_rppi_pair_counts, "ast_rppi_pair_counts") if rppi else \
+            (lib.ast_tpcf_pair_counts, "ast_tpcf_pair_counts")
+        check(count(ptr(work), ws_bytes, n, box, los, ptr(s_d), ns, ptr(mu_d), nmu, *tail, ptr(counts), st), name)
     return counts
 
 
@@ -1681,6 +1691,14 @@ def tpcf_jackknife_counts(pos1, nsub, s_edges, mu_edges=None, pos2=None, boxsize
     cell; ASTRILD_TPCF_JK_LDS=0 forces the table into global memory, whatever its size."""
     periodic = boxsize is not None
     s, mu = check_tpcf_edges(s_edges, mu_edges, boxsize, periodic=periodic)
+    return _tpcf_jk_counts(pos1, nsub, s, mu, pos2, boxsize, vel1, vel2, los, tags1, tags2, extent)
+
+
+def _tpcf_jk_counts(pos1, nsub, s, mu, pos2, boxsize, vel1, vel2, los, tags1, tags2, extent, rppi=False):
+    """tpcf_jackknife_counts after its edge check (``s`` / ``mu``: checked edges): the other checks, ast_tpcf_jk_prepare,
+    the device checks and ast_tpcf_jk_counts.  ``rppi``: ``s`` / ``mu`` are r_p / pi edges and the counts are
+    ast_rppi_jk_counts', on the same prepared workspace."""
+    periodic = boxsize is not None
     if los not in (0, 1, 2):
         raise ValueError(f"los must be 0, 1 or 2, got {los}")
     auto = pos2 is None
@@ -1723,9 +1741,76 @@ def tpcf_jackknife_counts(pos1, nsub, s_edges, mu_edges=None, pos2=None, boxsize
     shape = (ns, nmu) if nmu else (ns,)
     counts = torch.empty(shape, dtype=torch.int64, device=p1.device)
     ends = torch.empty((ntot,) + shape, dtype=torch.int64, device=p1.device)
-    check(lib.ast_tpcf_jk_counts(ptr(work), ws_bytes, n1, n2, int(auto), box, los, ptr(s_d), ns, ptr(mu_d), nmu, ntot,
-                                 int(single), int(force_global), ptr(counts), ptr(ends), st), "ast_tpcf_jk_counts")
+    count, name = (lib.ast_rppi_jk_counts, "ast_rppi_jk_counts") if rppi else \
+        (lib.ast_tpcf_jk_counts, "ast_tpcf_jk_counts")
+    tail = (int(force_global), _rppi_plan()) if rppi else (int(force_global),)
+    check(count(ptr(work), ws_bytes, n1, n2, int(auto), box, los, ptr(s_d), ns, ptr(mu_d), nmu, ntot, int(single), *tail,
+                ptr(counts), ptr(ends), st), name)
     return counts, ends
+
+
+# ------------------------------------------------------------------ xi(r_p, pi): pairs across and along a line of sight
+def check_rp_pi_edges(rp_edges, pi_edges, boxsize, periodic=True):
+    """The argument checks of an (r_p, pi) pair count, on the host: fp64 edges ``(rp, pi)`` or ValueError.  Each set
+    of edges: at least two values, finite, >= 0, strictly increasing; ``periodic``: ``boxsize`` positive and finite,
+    and both top edges below boxsize / 3 (``periodic=False``, open boundaries: ``boxsize`` is not looked at and the
+    top edges are free); at most 1000 bins per axis and ``ast_tpcf_max_bins()`` bins in all."""
+    if periodic:
+        boxsize = float(boxsize)
+        if not (np.isfinite(boxsize) and boxsize > 0):
+            raise ValueError(f"boxsize must be positive and finite, got {boxsize}")
+    top = boxsize / 3.0 if periodic else None
+    rp = _check_edges(rp_edges, "rp edge", top=top)
+    if pi_edges is None:
+        raise ValueError("pi edges must be at least two finite, non-negative, strictly increasing values")
+    pi = _check_edges(pi_edges, "pi edge", top=top)
+    nrp, npi = len(rp) - 1, len(pi) - 1
+    if nrp > 1000 or npi > 1000 or nrp * npi > _lib.lib().ast_tpcf_max_bins():
+        raise ValueError(f"{nrp} x {npi} bins: at most 1000 edges per axis and {_lib.lib().ast_tpcf_max_bins()} bins")
+    return rp, pi
+
+
+def rp_pi_pair_counts(pos, boxsize, rp_edges, pi_edges, vel=None, los=2):
+    """Unordered pair counts of a periodic box in bins of (r_p, pi) (ast_tpcf_prepare / ast_rppi_pair_counts): an int64
+    device tensor (n_rp, n_pi), the twin of tpcf_pair_counts.  Minimum image p_c per axis as there; with a < b the axes
+    other than ``los``, rp^2 = p_a^2 + p_b^2 and pi = p_los; a pair counts in (k, l) when rp_k^2 < rp^2 <= rp_{k+1}^2
+    and pi_l < pi <= pi_{l+1}, so one with pi on the lowest pi edge (pi = 0 when that edge is 0) or r_p on the lowest
+    r_p edge is in no bin, and coincident points never count.  ``vel``, the dtypes, ``los`` and the ValueErrors (edges:
+    check_rp_pi_edges) as tpcf_pair_counts.  ASTRILD_TPCF_CELLS=0 forces one cell; ASTRILD_RPPI_ANISO=0 plans the
+    isotropic grid of cells sqrt(rp_max^2 + pi_max^2) wide instead of cells r_p,max across and pi_max along ``los``."""
+    rp, pi = check_rp_pi_edges(rp_edges, pi_edges, boxsize)
+    if los not in (0, 1, 2):
+        raise ValueError(f"los must be 0, 1 or 2, got {los}")
+    one = _pair_sample(pos, vel, "pos must be (N, 3), got {p}", "vel must be (N, 3) like pos, got {v}")
+    return _tpcf_counts([one], None, rp, pi, float(boxsize), True, los, rppi=True)
+
+
+def rp_pi_cross_counts(pos1, pos2, rp_edges, pi_edges, boxsize=None, vel1=None, vel2=None, los=2):
+    """Pair counts between two samples in bins of (r_p, pi) (ast_tpcf_cross_prepare / ast_rppi_cross_counts): an int64
+    device tensor (n_rp, n_pi) of every pair (i of ``pos1``, j of ``pos2``); ``pos2=None``: the unordered pairs of
+    ``pos1``.  The twin of tpcf_cross_counts - ``boxsize`` (None: open boundaries), ``vel1`` / ``vel2``, dtypes,
+    ``los`` and ValueErrors as there - with the geometry, bins and switches of rp_pi_pair_counts."""
+    periodic = boxsize is not None
+    rp, pi = check_rp_pi_edges(rp_edges, pi_edges, boxsize, periodic=periodic)
+    if los not in (0, 1, 2):
+        raise ValueError(f"los must be 0, 1 or 2, got {los}")
+    auto = pos2 is None
+    if auto and vel2 is not None:
+        raise ValueError("vel2 given without pos2")
+    sample = lambda pos, vel, name: _pair_sample(pos, vel, name + " must be (N, 3), got {p}",
+                                                 "the velocities of " + name + " must be (N, 3) like it, got {v}")
+    sets = [sample(pos1, vel1, "pos1"), (None, None, 0) if auto else sample(pos2, vel2, "pos2")]
+    return _tpcf_counts(sets, auto, rp, pi, float(boxsize) if periodic else 0.0, periodic, los, rppi=True)
+
+
+def rp_pi_jackknife_counts(pos1, nsub, rp_edges, pi_edges, pos2=None, boxsize=None, vel1=None, vel2=None, los=2,
+                           tags1=None, tags2=None, extent=None):
+    """rp_pi_cross_counts with the endpoint table of a leave-one-region-out jackknife (ast_tpcf_jk_prepare /
+    ast_rppi_jk_counts): ``(counts, ends)``, int64 device tensors of (n_rp, n_pi) and (ntot, n_rp, n_pi).  The twin of
+    tpcf_jackknife_counts: regions, tags, ``extent``, the identities ``ends.sum(0) == 2 counts`` and ``2 counts -
+    ends[k]``, ValueErrors and ASTRILD_TPCF_JK_LDS as there; geometry, bins and switches as rp_pi_pair_counts."""
+    rp, pi = check_rp_pi_edges(rp_edges, pi_edges, boxsize, periodic=boxsize is not None)
+    return _tpcf_jk_counts(pos1, nsub, rp, pi, pos2, boxsize, vel1, vel2, los, tags1, tags2, extent, rppi=True)
 
 
 # ------------------------------------------------------------------ pairwise-velocity moments in a box

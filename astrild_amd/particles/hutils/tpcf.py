@@ -58,7 +58,22 @@ source fixes it, without a check against the library itself:
   leave-one-subvolume-out resampling, every leave-one-out count of a term from one pass over its pairs; the weights,
   the identity behind the single pass and what is recalled rather than checked are in its docstring.
 
-``nthreads`` is accepted and ignored.
+* **xi(r_p, pi) and w_p(r_p)** (``rp_pi_tpcf``, ``wp``, ``rp_pi_tpcf_jackknife``, ``wp_jackknife``: halotools'
+  functions of those names, which the reference never calls): with ``los`` the line of sight and a < b the two other
+  axes, ``p_c`` the per-axis separation above (minimum image with a ``period``), ``rp^2 = p_a^2 + p_b^2`` and
+  ``pi = p_los``, fp64.  **Binning**: halotools differences the cumulative counts of ``npairs_xy_z`` (``r_p <= rp_k``
+  and ``pi <= pi_l``; recalled from its source, not checked against the library), so a pair lands in bin (k, l) when
+  ``rp_k^2 < rp^2 <= rp_{k+1}^2`` and ``pi_l < pi <= pi_{l+1}``, the r_p edges squared once in fp64 and the pi edges
+  compared as given.  A pair with pi exactly on the lowest pi edge (pi = 0 when that edge is 0) is in no bin; a pair
+  with r_p = 0 is in no bin when the lowest r_p edge is 0; coincident objects never count.  Both sets of edges are
+  finite, >= 0 and strictly increasing, and with a ``period`` both top edges are below period / 3.  **Bin volume**
+  (analytic randoms): ``RR_kl = N^2 pi (rp_{k+1}^2 - rp_k^2) 2 (pi_{l+1} - pi_l) / L^3``, the two cylinder shells on
+  either side of an object, and ``N1 N2`` for the cross term; everything else - the return conventions, user randoms,
+  open boundaries, the five estimators and ``return_counts`` - is what is said above for ``s_mu_tpcf``, from the same
+  ordered-count conventions.  ``w_p = 2 sum_l xi(r_p, pi_l) dpi_l`` (``wp_from_xi``) over ``pi_bins``, by default
+  halotools' single bin ``[0, pi_max]``; that halotools sums xi this way is recalled, not checked.
+
+``nthreads`` / ``num_threads`` and ``seed`` are accepted and ignored.
 """
 from typing import Optional, Union
 
@@ -72,26 +87,37 @@ def _check_estimator(estimator):
         raise ValueError(f"estimator {estimator!r}: one of {', '.join(ESTIMATORS)}")
 
 
-def _xi(dd_unordered, n, boxsize, s_edges, mu_edges=None):
-    """``2 DD / RR - 1`` with the analytic RR of a periodic box; ``mu_edges`` None: per s bin only."""
+def _bin_volume(s_edges, mu_edges=None, rppi=False):
+    """The volume that a bin offers the second object of an ordered pair: the shell ``(4 pi / 3)(s_{k+1}^3 - s_k^3)``,
+    times ``dmu`` with ``mu_edges``; ``rppi``: the two cylinder shells on either side of the first object,
+    ``pi (rp_{k+1}^2 - rp_k^2) x 2 (pi_{l+1} - pi_l)``."""
     s = np.asarray(s_edges, dtype=np.float64)
+    if rppi:
+        return np.outer(np.pi * (s[1:] ** 2 - s[:-1] ** 2), 2.0 * np.diff(np.asarray(mu_edges, dtype=np.float64)))
     shell = (4.0 * np.pi / 3.0) * (s[1:] ** 3 - s[:-1] ** 3)
     if mu_edges is not None:
         shell = np.outer(shell, np.diff(np.asarray(mu_edges, dtype=np.float64)))
-    rr = float(n) * float(n) * shell / float(boxsize) ** 3
+    return shell
+
+
+def _xi(dd_unordered, n, boxsize, s_edges, mu_edges=None, rppi=False):
+    """``2 DD / RR - 1`` with the analytic RR of a periodic box over ``_bin_volume``; ``mu_edges`` None: per s bin only."""
+    rr = float(n) * float(n) * _bin_volume(s_edges, mu_edges, rppi) / float(boxsize) ** 3
     with np.errstate(divide="ignore", invalid="ignore"):
         return 2.0 * dd_unordered.astype(np.float64) / rr - 1.0
 
 
-def _counts(pos, boxsize, s_edges, mu_edges, vel, los):
+def _counts(pos, boxsize, s_edges, mu_edges, vel, los, rppi=False):
     from ... import device as dev
+    if rppi:
+        return dev.to_numpy(dev.rp_pi_pair_counts(pos, boxsize, s_edges, mu_edges, vel=vel, los=los))
     return dev.to_numpy(dev.tpcf_pair_counts(pos, boxsize, s_edges, mu_edges=mu_edges, vel=vel, los=los))
 
 
-def _cross(pos1, pos2, boxsize, s_edges, mu_edges, vel1=None, vel2=None, los=2):
+def _cross(pos1, pos2, boxsize, s_edges, mu_edges, vel1=None, vel2=None, los=2, rppi=False):
     from ... import device as dev
-    return dev.to_numpy(dev.tpcf_cross_counts(pos1, pos2, s_edges, mu_edges=mu_edges, boxsize=boxsize, vel1=vel1,
-                                              vel2=vel2, los=los))
+    count = dev.rp_pi_cross_counts if rppi else dev.tpcf_cross_counts
+    return dev.to_numpy(count(pos1, pos2, s_edges, mu_edges, boxsize=boxsize, vel1=vel1, vel2=vel2, los=los))
 
 
 def _estimate(estimator, dd, dr, rr, na, nb, nr):
@@ -114,8 +140,10 @@ _USES_DR = ("Davis-Peebles", "Hewett", "Hamilton", "Landy-Szalay")
 _USES_RR = ("Natural", "Hewett", "Hamilton", "Landy-Szalay")
 
 
-def _correlate(pos1, pos2, randoms, s, mu, period, estimator, do_auto, do_cross, vel1=None, vel2=None, los=2):
-    """The xi terms asked for and the dict of raw counts; ``s`` / ``mu`` are checked edges."""
+def _correlate(pos1, pos2, randoms, s, mu, period, estimator, do_auto, do_cross, vel1=None, vel2=None, los=2,
+               rppi=False):
+    """The xi terms asked for and the dict of raw counts; ``s`` / ``mu`` are checked edges - with ``rppi`` the r_p / pi
+    edges, and the counters and the bin volume are those of (r_p, pi)."""
     _check_estimator(estimator)
     if not (do_auto or do_cross):
         raise ValueError("do_auto and do_cross are both False: nothing to compute")
@@ -129,36 +157,34 @@ def _correlate(pos1, pos2, randoms, s, mu, period, estimator, do_auto, do_cross,
 
     def unordered(pos, vel):
         if period is not None:
-            return _counts(pos, period, s, mu, vel, los)
-        return _cross(pos, None, None, s, mu, vel1=vel, los=los)
+            return _counts(pos, period, s, mu, vel, los, rppi)
+        return _cross(pos, None, None, s, mu, vel1=vel, los=los, rppi=rppi)
 
     c = {}
     if auto1:
         c["D1D1"] = unordered(pos1, vel1)
     if cross:
-        c["D1D2"] = _cross(pos1, pos2, period, s, mu, vel1=vel1, vel2=vel2, los=los)
+        c["D1D2"] = _cross(pos1, pos2, period, s, mu, vel1=vel1, vel2=vel2, los=los, rppi=rppi)
     if auto2:
         c["D2D2"] = unordered(pos2, vel2)
     xi = {}
     if randoms is None:
         if auto1:
-            xi[11] = _xi(c["D1D1"], n1, period, s, mu)
+            xi[11] = _xi(c["D1D1"], n1, period, s, mu, rppi)
         if auto2:
-            xi[22] = _xi(c["D2D2"], n2, period, s, mu)
+            xi[22] = _xi(c["D2D2"], n2, period, s, mu, rppi)
         if cross:
-            shell = (4.0 * np.pi / 3.0) * (s[1:] ** 3 - s[:-1] ** 3)
-            if mu is not None:
-                shell = np.outer(shell, np.diff(mu))
+            shell = _bin_volume(s, mu, rppi)
             with np.errstate(divide="ignore", invalid="ignore"):
                 xi[12] = f64(c["D1D2"]) / (float(n1) * float(n2) * shell / float(period) ** 3) - 1.0
     else:
         nr = len(randoms)
         dr1 = dr2 = rr = None
         if estimator in _USES_DR:
-            c["D1R"] = _cross(pos1, randoms, period, s, mu, vel1=vel1, los=los)
+            c["D1R"] = _cross(pos1, randoms, period, s, mu, vel1=vel1, los=los, rppi=rppi)
             dr1 = f64(c["D1R"])
             if auto2:
-                c["D2R"] = _cross(pos2, randoms, period, s, mu, vel1=vel2, los=los)
+                c["D2R"] = _cross(pos2, randoms, period, s, mu, vel1=vel2, los=los, rppi=rppi)
                 dr2 = f64(c["D2R"])
         if estimator in _USES_RR:
             c["RR"] = unordered(randoms, None)
@@ -323,7 +349,8 @@ def jackknife_tags(pos, nsub, lo, hi):
     return ((i[:, 0] * nsub[1] + i[:, 1]) * nsub[2] + i[:, 2]).astype(np.int32)
 
 
-def jackknife_from_counts(c, n1, m1, nr, mr, n2=None, m2=None, estimator="Natural", do_auto=True, do_cross=True):
+def jackknife_from_counts(c, n1, m1, nr, mr, n2=None, m2=None, estimator="Natural", do_auto=True, do_cross=True,
+                          transform=None):
     """xi of the full sample and its jackknife covariance from integer counts, on the host in fp64 (no GPU).
 
     ``c``: term -> ``(counts, ends)`` under ``D1D1, D1D2, D2D2, D1R, D2R, RR`` (those the estimator and the flags need),
@@ -333,7 +360,9 @@ def jackknife_from_counts(c, n1, m1, nr, mr, n2=None, m2=None, estimator="Natura
     ``_estimate`` as for the full sample.  ``cov = (n - 1) / n sum_k (xi_k - mean)(xi_k - mean)^T`` over all n regions,
     empty ones included, mean the mean of the xi_k, xi flattened per bin.  Returns, in halotools' order, ``(xi, cov)``
     for one sample, ``(xi_11, xi_12, xi_22, cov_11, cov_12, cov_22)`` for two, ``(xi_12, cov_12)`` with ``do_cross``
-    only and ``(xi_11, xi_22, cov_11, cov_22)`` with ``do_auto`` only; xi of shape B, cov (prod B, prod B)."""
+    only and ``(xi_11, xi_22, cov_11, cov_22)`` with ``do_auto`` only; xi of shape B, cov (prod B, prod B).
+    ``transform``: a function applied to the full-sample xi and to every xi_k (each of shape B) before the covariance,
+    which is then that of the transformed statistic (``wp_jackknife``: w_p from xi(r_p, pi))."""
     _check_estimator(estimator)
     if not (do_auto or do_cross):
         raise ValueError("do_auto and do_cross are both False: nothing to compute")
@@ -357,9 +386,11 @@ def jackknife_from_counts(c, n1, m1, nr, mr, n2=None, m2=None, estimator="Natura
 
     def term(a, b):
         dd, dr = ("D1D2" if a != b else f"D{a}D{a}"), f"D{a}R"
-        xi = _estimate(estimator, ordered(dd), ordered(dr), ordered("RR"), full[a], full[b], nr)
-        xik = np.stack([np.asarray(_estimate(estimator, ordered(dd, k), ordered(dr, k), ordered("RR", k), left[a][k],
-                                             left[b][k], left["R"][k])).reshape(-1) for k in range(n)])
+        stat = transform if transform is not None else (lambda x: x)
+        xi = stat(_estimate(estimator, ordered(dd), ordered(dr), ordered("RR"), full[a], full[b], nr))
+        xik = np.stack([np.asarray(stat(_estimate(estimator, ordered(dd, k), ordered(dr, k), ordered("RR", k),
+                                                  left[a][k], left[b][k], left["R"][k]))).reshape(-1)
+                        for k in range(n)])
         with np.errstate(invalid="ignore"):
             d = xik - xik.mean(axis=0)
             return xi, (n - 1.0) / n * (d.T @ d)
@@ -407,6 +438,16 @@ def tpcf_jackknife(sample1, randoms, rbins, Nsub=[5, 5, 5], sample2=None, period
     if randoms is None:
         raise ValueError("tpcf_jackknife needs randoms")
     s, mu = dev.check_tpcf_edges(rbins, mu_bins, period, periodic=period is not None)
+    return _jackknife(sample1, randoms, s, mu, Nsub, sample2, period, do_auto, do_cross, estimator, los, return_counts)
+
+
+def _jackknife(sample1, randoms, s, mu, Nsub, sample2, period, do_auto, do_cross, estimator, los, return_counts,
+               rppi=False, transform=None):
+    """``tpcf_jackknife`` after its argument checks: the regions, one counting pass per term and
+    ``jackknife_from_counts`` (with its ``transform``).  ``s`` / ``mu``: checked edges; ``rppi``: r_p / pi edges and
+    ``device.rp_pi_jackknife_counts``."""
+    from ... import device as dev
+
     host = lambda a: dev.to_numpy(a) if hasattr(a, "is_cuda") else np.asarray(a)
     sets = {"1": host(sample1), "R": host(randoms)}
     if sample2 is not None:
@@ -422,8 +463,9 @@ def tpcf_jackknife(sample1, randoms, rbins, Nsub=[5, 5, 5], sample2=None, period
     m = {k: np.bincount(t, minlength=ntot) for k, t in tags.items()}
 
     def count(a, b=None):
-        out = dev.tpcf_jackknife_counts(sets[a], ntot, s, mu, pos2=None if b is None else sets[b], boxsize=period,
-                                        los=los, tags1=tags[a], tags2=None if b is None else tags[b])
+        counter = dev.rp_pi_jackknife_counts if rppi else dev.tpcf_jackknife_counts
+        out = counter(sets[a], ntot, s, mu, pos2=None if b is None else sets[b], boxsize=period, los=los,
+                      tags1=tags[a], tags2=None if b is None else tags[b])
         return tuple(dev.to_numpy(x) for x in out)
 
     two = sample2 is not None
@@ -442,8 +484,97 @@ def tpcf_jackknife(sample1, randoms, rbins, Nsub=[5, 5, 5], sample2=None, period
     if estimator in _USES_RR:
         c["RR"] = count("R")
     out = jackknife_from_counts(c, len(sets["1"]), m["1"], len(sets["R"]), m["R"], len(sets["2"]) if two else None,
-                                m.get("2"), estimator, do_auto, do_cross)
+                                m.get("2"), estimator, do_auto, do_cross, transform=transform)
     return out + (c,) if return_counts else out
+
+
+def wp_from_xi(xi, pi_bins):
+    """``w_p(r_p) = 2 sum_l xi(r_p, pi_l) dpi_l`` over the pi bins (the last axis of ``xi``), halotools' sum in ``wp``.
+    Host numpy, fp64."""
+    xi = np.asarray(xi, dtype=np.float64)
+    pi = np.asarray(pi_bins, dtype=np.float64).reshape(-1)
+    if xi.ndim < 1 or xi.shape[-1] != len(pi) - 1:
+        raise ValueError(f"xi has {xi.shape[-1] if xi.ndim else 0} pi bins, pi_bins gives {len(pi) - 1}")
+    return 2.0 * np.sum(xi * np.diff(pi), axis=-1)
+
+
+def _wp_pi_bins(pi_max, pi_bins):
+    """The pi edges of ``wp``: halotools' single bin ``[0, pi_max]``, or ``pi_bins``, which must end at ``pi_max``."""
+    if pi_bins is None:
+        return np.array([0.0, float(pi_max)])
+    pi = np.asarray(pi_bins, dtype=np.float64).reshape(-1)
+    if len(pi) < 2 or pi[-1] != float(pi_max):
+        raise ValueError(f"pi_bins must end at pi_max = {pi_max}, got {pi.tolist()}")
+    return pi
+
+
+def rp_pi_tpcf(sample1, rp_bins, pi_bins, sample2=None, randoms=None, period=None, do_auto: bool = True,
+               do_cross: bool = True, estimator: str = "Natural", los: int = 2, return_counts: bool = False,
+               num_threads: int = 1):
+    """xi(r_p, pi) with halotools' ``rp_pi_tpcf`` arguments (module docstring): each term of shape (len(rp_bins) - 1,
+    len(pi_bins) - 1), returned as ``s_mu_tpcf`` returns its terms.  The samples are used as given, with axis ``los``
+    the line of sight.  With ``return_counts`` also the dict of raw int64 counts.  ``num_threads`` is ignored."""
+    from ... import device as dev
+
+    _check_estimator(estimator)
+    if not (do_auto or do_cross):
+        raise ValueError("do_auto and do_cross are both False: nothing to compute")
+    if period is None and randoms is None:
+        raise ValueError("period=None (open boundaries) needs randoms")
+    rp, pi = dev.check_rp_pi_edges(rp_bins, pi_bins, period, periodic=period is not None)
+    xi, c = _correlate(sample1, sample2, randoms, rp, pi, period, estimator, do_auto, do_cross, los=los, rppi=True)
+    return (xi, c) if return_counts else xi
+
+
+def wp(sample1, rp_bins, pi_max, sample2=None, randoms=None, period=None, do_auto: bool = True, do_cross: bool = True,
+       estimator: str = "Natural", los: int = 2, pi_bins=None, return_counts: bool = False, num_threads: int = 1):
+    """The projected correlation function ``w_p(r_p) = 2 sum_l xi(r_p, pi_l) dpi_l`` with halotools' ``wp`` arguments:
+    each term of shape (len(rp_bins) - 1,), returned as ``rp_pi_tpcf`` returns its terms.  ``pi_bins`` None:
+    halotools' single bin ``[0, pi_max]``; given, they must end at ``pi_max``.  With ``return_counts`` also the dict
+    of raw int64 (r_p, pi) counts.  ``num_threads`` is ignored."""
+    pi = _wp_pi_bins(pi_max, pi_bins)
+    xi, c = rp_pi_tpcf(sample1, rp_bins, pi, sample2=sample2, randoms=randoms, period=period, do_auto=do_auto,
+                       do_cross=do_cross, estimator=estimator, los=los, return_counts=True)
+    out = tuple(wp_from_xi(x, pi) for x in xi) if isinstance(xi, tuple) else wp_from_xi(xi, pi)
+    return (out, c) if return_counts else out
+
+
+def _rp_pi_jackknife(name, sample1, randoms, rp_bins, pi, Nsub, sample2, period, do_auto, do_cross, estimator, los,
+                     return_counts, transform=None):
+    from ... import device as dev
+
+    _check_estimator(estimator)
+    if not (do_auto or do_cross):
+        raise ValueError("do_auto and do_cross are both False: nothing to compute")
+    if randoms is None:
+        raise ValueError(f"{name} needs randoms")
+    rp, pi = dev.check_rp_pi_edges(rp_bins, pi, period, periodic=period is not None)
+    return _jackknife(sample1, randoms, rp, pi, Nsub, sample2, period, do_auto, do_cross, estimator, los, return_counts,
+                      rppi=True, transform=transform)
+
+
+def rp_pi_tpcf_jackknife(sample1, randoms, rp_bins, pi_bins, Nsub=[5, 5, 5], sample2=None, period=None,
+                         do_auto: bool = True, do_cross: bool = True, estimator: str = "Natural", los: int = 2,
+                         return_counts: bool = False, num_threads: int = 1, seed=None):
+    """xi(r_p, pi) and its covariance matrix from leave-one-subvolume-out resampling, with halotools'
+    ``rp_pi_tpcf_jackknife`` arguments: ``tpcf_jackknife`` (regions, weights, estimate, return order, ``return_counts``)
+    on the (r_p, pi) counts of ``device.rp_pi_jackknife_counts``; xi of shape (n_rp, n_pi), cov (n_rp n_pi, n_rp n_pi).
+    ``num_threads`` and ``seed`` are accepted and ignored."""
+    return _rp_pi_jackknife("rp_pi_tpcf_jackknife", sample1, randoms, rp_bins, pi_bins, Nsub, sample2, period, do_auto,
+                            do_cross, estimator, los, return_counts)
+
+
+def wp_jackknife(sample1, randoms, rp_bins, pi_max, Nsub=[5, 5, 5], sample2=None, period=None, do_auto: bool = True,
+                 do_cross: bool = True, estimator: str = "Natural", los: int = 2, pi_bins=None,
+                 return_counts: bool = False, num_threads: int = 1, seed=None):
+    """w_p(r_p) of the full sample and its jackknife covariance, with halotools' ``wp_jackknife`` arguments, in
+    ``tpcf_jackknife``'s return order with terms of shape (n_rp,) and cov (n_rp, n_rp).  The covariance is that of the
+    per-region ``w_p,k = wp_from_xi(xi_k)``, formed from the xi_k of the one counting pass of
+    ``rp_pi_tpcf_jackknife`` (no second pass over the pairs).  ``pi_bins`` as ``wp``; ``return_counts`` appends the
+    dict of raw (r_p, pi) ``(counts, ends)``.  ``num_threads`` and ``seed`` are accepted and ignored."""
+    pi = _wp_pi_bins(pi_max, pi_bins)
+    return _rp_pi_jackknife("wp_jackknife", sample1, randoms, rp_bins, pi, Nsub, sample2, period, do_auto, do_cross,
+                            estimator, los, return_counts, transform=lambda xi: wp_from_xi(xi, pi))
 
 
 def tpcf_multipole(xi_s_mu, mu_bins, order: int = 0):

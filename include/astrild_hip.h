@@ -992,6 +992,44 @@ int ast_tpcf_jk_counts(void* work_d, size_t work_bytes, size_t n1, size_t n2, in
                        const double* s_edges_d, int ns, const double* mu_edges_d, int nmu, int nsub, int single_cell,
                        int force_global, unsigned long long* counts_d, unsigned long long* ends_d, void* stream);
 
+/* Pair counts in bins of (r_p, pi), the separation across and along a line of sight: what halotools' rp_pi_tpcf, wp
+ * and their jackknife variants count (npairs_xy_z; the members of mock_observables beside the s_mu_tpcf that
+ * particles/hutils/tpcf.py:7-9 imports).  The prepare calls and the workspaces do not depend on the geometry: each
+ * count below runs on the workspace of its ast_tpcf_* twin, prepared by that twin's prepare call and sized by its
+ * *_workspace_bytes with (nrp, npi) in place of (ns, nmu).
+ *
+ * With a < b the axes other than los, per pair and in fp64: p_c = |x_i[c] - x_j[c]|, with boxsize > 0 the minimum
+ * image p_c = min(p_c, boxsize - p_c) (ast_tpcf_cross_counts' arithmetic, bit for bit); rp2 = p_a p_a + p_b p_b and
+ * pi = p_los.  The pair counts in bin (k, l) when rp_k^2 < rp2 <= rp_{k+1}^2 (rp_edges_d: nrp + 1 edges, squared in
+ * fp64 on the device) and pi_l < pi <= pi_{l+1} (pi_edges_d: npi + 1 edges, compared as given; npi >= 1).  So a pair
+ * with pi on the lowest pi edge (pi = 0 when that edge is 0) or rp2 on the lowest r_p edge squared is in no bin, and
+ * coincident points never count.  counts_d[k * npi + l], written, not accumulated; exact for n < 2^31.  Limits as
+ * ast_tpcf_workspace_bytes: at most 1000 bins per axis and nrp * npi <= ast_tpcf_max_bins().
+ *
+ * Pair finder: the cell grid of the twin with cells of a width per axis.  plan == 0: the reach is the top pi edge
+ * along los and the top r_p edge across.  Periodic: floor(boxsize / (reach (1 + 1e-6))) cells on an axis, at most
+ * 1024, and 1 where that is fewer than 3 (the minimum image then finds the pairs of that axis); fewer cells on every
+ * axis while the grid exceeds the workspace's cell capacity.  Open: the twin's rule over the bounding box, per axis.
+ * plan == 1: the isotropic grid of ast_pairvel_moments' AST_PAIRVEL_LOS, cells of sqrt(rp_top^2 + pi_top^2) on every
+ * axis.  single_cell != 0 forces one cell.  The counts do not depend on the plan.
+ *
+ * ast_rppi_pair_counts, ast_rppi_cross_counts, ast_rppi_jk_counts: all other arguments, the outputs (counts_d, and
+ * ends_d[nsub * nrp * npi] of the jackknife) and the early returns are those of ast_tpcf_pair_counts,
+ * ast_tpcf_cross_counts and ast_tpcf_jk_counts. */
+/* halotools rp_pi_tpcf / wp for one sample in a periodic box (particles/hutils/tpcf.py:7-9) */
+int ast_rppi_pair_counts(void* work_d, size_t work_bytes, size_t n, double boxsize, int los, const double* rp_edges_d,
+                         int nrp, const double* pi_edges_d, int npi, int single_cell, int plan,
+                         unsigned long long* counts_d, void* stream);
+/* halotools rp_pi_tpcf / wp with sample2= or randoms=, periodic or open (particles/hutils/tpcf.py:7-9) */
+int ast_rppi_cross_counts(void* work_d, size_t work_bytes, size_t n1, size_t n2, int auto_pairs, double boxsize,
+                          int los, const double* rp_edges_d, int nrp, const double* pi_edges_d, int npi,
+                          int single_cell, int plan, unsigned long long* counts_d, void* stream);
+/* halotools rp_pi_tpcf_jackknife / wp_jackknife (particles/hutils/tpcf.py:7-9) */
+int ast_rppi_jk_counts(void* work_d, size_t work_bytes, size_t n1, size_t n2, int auto_pairs, double boxsize, int los,
+                       const double* rp_edges_d, int nrp, const double* pi_edges_d, int npi, int nsub, int single_cell,
+                       int force_global, int plan, unsigned long long* counts_d, unsigned long long* ends_d,
+                       void* stream);
+
 /* ------------------------------------------------- pairwise-velocity moments of one or two samples in a box */
 
 /* Count, sum v and sum v^2 per separation bin of the pairwise velocity of one or two samples, in a periodic cube or
