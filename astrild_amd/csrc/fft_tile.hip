@@ -1370,7 +1370,8 @@ struct EdgeFallCache {
         if (n == 1024) edge_fall_kernel<32, 32, 16><<<blocks, nt, 0, s>>>(d, (unsigned)tiles, (int)nz, kf);
         else if (n == 512) edge_fall_kernel<16, 32, 16><<<blocks, nt, 0, s>>>(d, (unsigned)tiles, (int)nz, kf);
         else edge_fall_kernel<16, 16, 16><<<blocks, nt, 0, s>>>(d, (unsigned)tiles, (int)nz, kf);
-        if (hipGetLastError() != hipSuccess) return nullptr;
+        // complete before it is cached: a later caller on ANOTHER stream reads the table with nothing ordering it behind `s`
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { (void)hipFree(d); return nullptr; }
         if (tabs.size() >= 4) { (void)hipFree(tabs.front().words); tabs.erase(tabs.begin()); }      // a few (N, L) at most
         tabs.push_back({dev, n, boxsize, d});
         return d;
@@ -1714,7 +1715,8 @@ struct LowkLaneCache {
         double2* d = nullptr;
         if (hipMalloc(&d, (size_t)lanes * 7 * 2 * sizeof(double2)) != hipSuccess) return nullptr;
         lowk_lane_kernel<<<2, 256, 0, s>>>(d, n, lanes);
-        if (hipGetLastError() != hipSuccess) return nullptr;
+        // complete before it is cached (as the edge table above: read later from any stream)
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { (void)hipFree(d); return nullptr; }
         tabs.push_back({dev, n, d});
         return d;
     }
@@ -1873,12 +1875,16 @@ struct SideStreamCache {
         int dev = 0;
         if (hipGetDevice(&dev) != hipSuccess) return nullptr;
         for (auto& e : all) if (e.dev == dev && e.main == main) return &e;
-        SideStream e{dev, main, nullptr, nullptr, nullptr};
-        if (hipStreamCreateWithFlags(&e.side, hipStreamNonBlocking) != hipSuccess) return nullptr;
-        if (hipEventCreateWithFlags(&e.in, hipEventDisableTiming) != hipSuccess) return nullptr;
-        if (hipEventCreateWithFlags(&e.done, hipEventDisableTiming) != hipSuccess) return nullptr;
         all.reserve(64);
         if (all.size() >= 64) return nullptr;              // pointers into `all` stay valid: it never reallocates
+        SideStream e{dev, main, nullptr, nullptr, nullptr};
+        if (hipStreamCreateWithFlags(&e.side, hipStreamNonBlocking) != hipSuccess) return nullptr;
+        if (hipEventCreateWithFlags(&e.in, hipEventDisableTiming) != hipSuccess ||
+            hipEventCreateWithFlags(&e.done, hipEventDisableTiming) != hipSuccess) {
+            if (e.in) (void)hipEventDestroy(e.in);
+            (void)hipStreamDestroy(e.side);
+            return nullptr;
+        }
         all.push_back(e);
         return &all.back();
     }

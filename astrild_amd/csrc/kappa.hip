@@ -447,6 +447,9 @@ extern "C" int ast_lens_plan_create(ast_lens_plan** out, int nc, double bsz) {
         if (e == hipSuccess) e = hipMalloc(&p->kout[0], sq);
         if (e == hipSuccess) e = hipMalloc(&p->kout[1], sq);
     }
+    // the two zero fills above go to the null stream, which orders nothing against a caller's non-blocking stream: they
+    // are complete before the plan is handed out (a fill that lands after the first use would wipe the map's corner)
+    if (e == hipSuccess && (!p->rows || embedded)) e = hipStreamSynchronize(nullptr);
     if (e != hipSuccess) {
         ast::set_error("ast_lens_plan_create: hipMalloc -> %s", hipGetErrorString(e));
         ast_lens_plan_destroy(p);

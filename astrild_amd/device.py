@@ -6,6 +6,7 @@ Arrays follow the reference's layouts: grids are ``(N, N, N)`` C order with
 axis 0 slowest (``value_map[x, y, z]``, power_spectrum_3d.py:142-148), particle
 positions ``(Np, 3)`` like pmesh's ``paint`` (stats_subfind.py:125-131).
 """
+import contextlib
 import ctypes as ct
 import itertools
 import os
@@ -145,6 +146,12 @@ def fft_plan(kind, dtype_code, lengths, batch=1, scale=1.0, inplace=False, strid
 
 def clear_plan_cache():
     _plan_cache.clear()
+
+
+def stream_key():
+    """(device, handle of the current stream): what lensing's hidden plan caches add to their keys.  A plan owns ONE set
+    of device buffers, so two streams must never share one; keyed this way every stream gets its own (Streams)."""
+    return torch.cuda.current_device(), int(torch.cuda.current_stream().cuda_stream)
 
 
 # ------------------------------------------------------------ mass assignment
@@ -884,6 +891,33 @@ def catalog_power_2d(pos1, mass1, nmesh, boxsize, window="tsc", interlaced=True,
 _power_scratch = {}
 
 
+@contextlib.contextmanager
+def _power_scratch_for(key, nbytes, device_):
+    """``with _power_scratch_for(key, nbytes, device) as scratch``: the ONE cached scratch tensor of the fused power
+    paths (another key releases it: peak memory at 1024^3), taken for a call on the current stream.  The stream and the
+    event of its last use travel with the tensor, as an attribute: the dict's values stay the tensors themselves (the
+    tests look them up, and tests/dirty_memory.py swaps the dict for a while).  A call on another stream waits for that
+    event first - two streams take turns on the scratch - and tells the allocator about the new stream, so that a
+    release (the ``clear()`` below) does not hand the block out again while that stream still works in it.  The end of
+    the use is recorded on the way out, also when the call raised: whatever it had queued still runs."""
+    cur = torch.cuda.current_stream()
+    scratch = _power_scratch.get(key)
+    if scratch is None:
+        _power_scratch.clear()
+        scratch = _power_scratch[key] = torch.empty(int(nbytes), dtype=torch.uint8, device=device_)
+        scratch.ast_last_use = None
+    last = getattr(scratch, "ast_last_use", None)
+    if last is not None and last[0] != cur:
+        cur.wait_event(last[1])
+        scratch.record_stream(cur)
+    try:
+        yield scratch
+    finally:
+        done = last[1] if last is not None else torch.cuda.Event()
+        done.record(cur)
+        scratch.ast_last_use = (cur, done)
+
+
 def power_sums_fused(field, boxsize, psum=None, mean=0.0, halo=None, lowk=True, binning=None):
     """(ksum, psum, nmodes) of the auto power of an fp32 cube of side 256/512/1024 through
     the fused tile-FFT + shell-binning path (the spectrum is never written to HBM).
@@ -894,21 +928,17 @@ def power_sums_fused(field, boxsize, psum=None, mean=0.0, halo=None, lowk=True, 
     n = field.shape[0]
     L = _lib.lib()
     key = (torch.cuda.current_device(), n)
-    scratch = _power_scratch.get(key)
-    if scratch is None:
-        _power_scratch.clear()
-        scratch = _power_scratch[key] = torch.empty(int(L.ast_fft_tile_power_scratch_bytes(n)), dtype=torch.uint8,
-                                                    device=field.device)
     if psum is None:
         psum = torch.zeros(n // 2 - 1, dtype=torch.float64, device=field.device)
     ksum, nmodes = shell_geometry(n, boxsize, binning=binning)
-    if halo is not None:                      # grid from paint(..., defer_fold=True)
-        check(L.ast_fft_tile_power_3d_halo(ptr(field), halo.rec_ptr, halo.window_code, ptr(scratch), scratch.numel(),
-                                           real_code(field), n, float(boxsize), float(mean), int(bool(lowk)), _bin_code(binning), ptr(psum), stream()),
-              "ast_fft_tile_power_3d_halo")
-        return ksum, psum, nmodes
-    check(L.ast_fft_tile_power_3d(ptr(field), ptr(scratch), scratch.numel(), real_code(field), n, float(boxsize),
-                                  float(mean), int(bool(lowk)), _bin_code(binning), ptr(psum), stream()), "ast_fft_tile_power_3d")
+    with _power_scratch_for(key, L.ast_fft_tile_power_scratch_bytes(n), field.device) as scratch:
+        if halo is not None:                  # grid from paint(..., defer_fold=True)
+            check(L.ast_fft_tile_power_3d_halo(ptr(field), halo.rec_ptr, halo.window_code, ptr(scratch), scratch.numel(),
+                                               real_code(field), n, float(boxsize), float(mean), int(bool(lowk)), _bin_code(binning), ptr(psum), stream()),
+                  "ast_fft_tile_power_3d_halo")
+        else:
+            check(L.ast_fft_tile_power_3d(ptr(field), ptr(scratch), scratch.numel(), real_code(field), n, float(boxsize),
+                                          float(mean), int(bool(lowk)), _bin_code(binning), ptr(psum), stream()), "ast_fft_tile_power_3d")
     return ksum, psum, nmodes
 
 
@@ -963,34 +993,27 @@ def power_sums_fused64(field, boxsize, psum=None, binning=None, halo=None, mean=
         # are loaded and the sixteen lowest shells come from double-precision sums over the grid (inside the call) - fp32
         # round-off of an O(1) field on shells of little power - as the fp32 tile pipeline takes its five lowest
         key32 = (torch.cuda.current_device(), n, "f32big")
-        scratch = _power_scratch.get(key32)
-        if scratch is None:
-            _power_scratch.clear()
-            scratch = _power_scratch[key32] = torch.empty(int(L.ast_fft32_big_power_scratch_bytes(n)), dtype=torch.uint8, device=field.device)
-        if halo is not None:                  # grid from paint(..., defer_fold=True): the fold rides on the z rows
-            check(L.ast_fft32_big_power_3d_halo(ptr(field), halo.rec_ptr, halo.window_code, ptr(scratch), scratch.numel(), n,
-                                                float(boxsize), _bin_code(binning), float(mean), ptr(psum), stream()),
-                  "ast_fft32_big_power_3d_halo")
-        else:
-            check(L.ast_fft32_big_power_3d(ptr(field), ptr(scratch), scratch.numel(), n, float(boxsize), _bin_code(binning), float(mean),
-                                           ptr(psum), stream()), "ast_fft32_big_power_3d")
+        with _power_scratch_for(key32, L.ast_fft32_big_power_scratch_bytes(n), field.device) as scratch:
+            if halo is not None:              # grid from paint(..., defer_fold=True): the fold rides on the z rows
+                check(L.ast_fft32_big_power_3d_halo(ptr(field), halo.rec_ptr, halo.window_code, ptr(scratch), scratch.numel(), n,
+                                                    float(boxsize), _bin_code(binning), float(mean), ptr(psum), stream()),
+                      "ast_fft32_big_power_3d_halo")
+            else:
+                check(L.ast_fft32_big_power_3d(ptr(field), ptr(scratch), scratch.numel(), n, float(boxsize), _bin_code(binning), float(mean),
+                                               ptr(psum), stream()), "ast_fft32_big_power_3d")
         return ksum, psum, nmodes
     key = (torch.cuda.current_device(), n, "f64")
-    scratch = _power_scratch.get(key)
-    if scratch is None:
-        _power_scratch.clear()
-        scratch = _power_scratch[key] = torch.empty(int(L.ast_fft64_power_scratch_bytes(n)), dtype=torch.uint8, device=field.device)
-    if field.dtype == torch.float32:          # an fp32 grid through the double passes (sizes without fp32 tile passes)
-        assert halo is None
-        check(L.ast_fft64_power_3d_f32(ptr(field), ptr(scratch), scratch.numel(), n, float(boxsize), _bin_code(binning), ptr(psum),
-                                       stream()), "ast_fft64_power_3d_f32")
-        return ksum, psum, nmodes
-    if halo is not None:                      # grid from paint(..., defer_fold=True)
-        check(L.ast_fft64_power_3d_halo(ptr(field), halo.rec_ptr, halo.window_code, ptr(scratch), scratch.numel(), n,
-                                        float(boxsize), _bin_code(binning), ptr(psum), stream()), "ast_fft64_power_3d_halo")
-        return ksum, psum, nmodes
-    check(L.ast_fft64_power_3d(ptr(field), ptr(scratch), scratch.numel(), n, float(boxsize), _bin_code(binning), ptr(psum), stream()),
-          "ast_fft64_power_3d")
+    with _power_scratch_for(key, L.ast_fft64_power_scratch_bytes(n), field.device) as scratch:
+        if field.dtype == torch.float32:      # an fp32 grid through the double passes (sizes without fp32 tile passes)
+            assert halo is None
+            check(L.ast_fft64_power_3d_f32(ptr(field), ptr(scratch), scratch.numel(), n, float(boxsize), _bin_code(binning), ptr(psum),
+                                           stream()), "ast_fft64_power_3d_f32")
+        elif halo is not None:                # grid from paint(..., defer_fold=True)
+            check(L.ast_fft64_power_3d_halo(ptr(field), halo.rec_ptr, halo.window_code, ptr(scratch), scratch.numel(), n,
+                                            float(boxsize), _bin_code(binning), ptr(psum), stream()), "ast_fft64_power_3d_halo")
+        else:
+            check(L.ast_fft64_power_3d(ptr(field), ptr(scratch), scratch.numel(), n, float(boxsize), _bin_code(binning), ptr(psum), stream()),
+                  "ast_fft64_power_3d")
     return ksum, psum, nmodes
 
 

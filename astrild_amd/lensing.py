@@ -12,7 +12,7 @@ import torch
 
 from . import _lib
 from ._lib import F64, check
-from .device import as_device, device, ptr, real_code, stream
+from .device import as_device, device, ptr, real_code, stream, stream_key
 
 
 # ------------------------------------------------------------------ a-7 stack
@@ -143,15 +143,21 @@ _lens_plans, _smooth_plans = {}, {}
 
 
 def lens_plan(nc, bsz):
-    key = (torch.cuda.current_device(), int(nc), float(bsz))
+    """The cached LensPlan of the CURRENT stream (a plan owns one set of device buffers: DESIGN.md, Streams)."""
+    key = (*stream_key(), int(nc), float(bsz))
     if key not in _lens_plans:
-        _lens_plans.clear()          # one resident plan: the spectra are 3 x 0.5 GB at nc = 4096
+        # one resident plan: the spectra are 3 x 0.5 GB at nc = 4096.  The plan that leaves may still have work queued on
+        # ANOTHER stream (the key holds the stream): its destructor frees the buffers with hipFree, which waits for the
+        # whole device first - that wait is what makes this safe.  Two streams that alternate on one (nc, bsz) therefore
+        # rebuild the plan, its three kernel spectra included, on every call (not timed): such callers hold a LensPlan each.
+        _lens_plans.clear()
         _lens_plans[key] = LensPlan(nc, bsz)
     return _lens_plans[key]
 
 
 def smooth_plan(npix):
-    key = (torch.cuda.current_device(), int(npix))
+    """The cached SmoothPlan of the CURRENT stream, as :func:`lens_plan`."""
+    key = (*stream_key(), int(npix))
     if key not in _smooth_plans:
         _smooth_plans[key] = SmoothPlan(npix)
     return _smooth_plans[key]
