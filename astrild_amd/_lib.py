@@ -218,6 +218,13 @@ SIGNATURES = {
     "ast_watershed_sums": (_i, [_vp, _i, _vp, _i, _sz, _vp, _vp, _vp]),
     "ast_watershed_edge_blocks": (_sz, [_i]),
     "ast_watershed_edges": (_i, [_vp, _i, _vp, _i, _vp, _sz, _vp, _vp, _vp]),
+    "ast_fof_workspace_bytes": (_sz, [_sz]),
+    "ast_fof_max_passes": (_i, [_sz]),
+    "ast_fof_prepare": (_i, [_vp, _i, _sz, _vp, _sz, _vp, _vp]),
+    "ast_fof_link": (_i, [_vp, _sz, _sz, _d, _i, _d, _d, _i, _i, _vp, _vp]),
+    "ast_fof_compress": (_i, [_vp, _sz, _sz, _vp, ct.POINTER(_i), _vp, _vp, _vp]),
+    "ast_fof_relabel": (_i, [_vp, _vp, _sz, _vp, _vp]),
+    "ast_fof_features": (_i, [_vp, _i, _vp, _i, _vp, _i, _sz, _vp, _vp, _vp, _sz, _d, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

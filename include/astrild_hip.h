@@ -1240,6 +1240,49 @@ size_t ast_watershed_edge_blocks(int npix);
 int ast_watershed_edges(const void* img_d, int dtype, const int* labels_d, int npix, long long* blocks_d, size_t cap,
                         long long* keys_d, void* saddle_d, void* stream);
 
+/* ------------------------------------------------- friends-of-friends group finder */
+
+/* Friends-of-friends groups of n < 2^31 particles (particles/hutils/fof.py).  Positions (n, 3), AST_F32 /
+ * AST_F64, widened to fp64.  Per axis a = |x_i - x_j|, with boxsize > 0 the minimum image a = min(a, L - a) (boxsize
+ * == 0: open).  Sphere (cylinder == 0): friends when (a_x^2 + a_y^2) + a_z^2 <= b_perp b_perp.  Cylinder along `los`:
+ * friends when a_a a_a + a_b a_b <= b_perp b_perp (a < b the two other axes) and a_los <= b_para.  A group is a
+ * connected component of the friendship graph.
+ *
+ * work_d: ast_fof_workspace_bytes(n) bytes (0: n out of range), contents undefined on entry; the calls below share it,
+ * in this order, on one stream.
+ * ast_fof_prepare writes the records and parent[i] = i into the workspace and bounds_d[6] = min x, y, z, max x, y, z
+ * (a NaN counts as -inf and +inf; n == 0: +inf, -inf), which the caller checks: periodic within [0, boxsize], open
+ * all finite.
+ * ast_fof_link plans the cell grid (cells at least b_perp wide; the cylinder: grid_cyl_plan's per-axis cells; at most
+ * one cell per 64 objects, or per AST_FOF_CELL_OBJECTS of the environment, and at least 27; single_cell != 0: one
+ * cell), sorts, and unites every friend pair in the parent forest; *links_d (device uint64, zeroed by the call)
+ * = the number of unordered friend pairs.  n < 2: only the zero.
+ * ast_fof_compress resolves the forest by pointer jumping, at most ast_fof_max_passes(n) = ceil(log2 n) + 1 passes (0:
+ * n out of range); pending_d: that many int32 of device scratch; *passes_host = the passes taken.  SYNCHRONOUS (one
+ * 4-byte read-back per pass); AST_ERR_LIMIT when the bound did not suffice, which no output of ast_fof_link can
+ * cause.  Then root_d[i] (int32) = the smallest index of i's group and size_d[r] (uint32, n entries, zeroed by the
+ * call) = the members of the group whose smallest index is r, 0 elsewhere.  n >= 1.
+ * ast_fof_relabel: labels_d[i] = table_d[root_d[i]] (int32, n entries each).
+ * ast_fof_features: for group g < ngroups with members members_d[offsets_d[g] .. offsets_d[g + 1]) (int32 particle
+ * indices; offsets int64) and first_d[g] (int64) its reference particle: s_i = pos_i - pos[first], with boxsize > 0
+ * wrapped once per axis (s > L/2 -> s - L, else s < -L/2 -> s + L); cm_d[g][3] = pos[first] + sum(w s) / sum(w),
+ * with boxsize > 0 wrapped once into [0, L); cmv_d[g][3] = sum(w v) / sum(w) when vel_d is given; weight_d[g] =
+ * sum(w); w = 1 without weights_d.  fp64; one wave per group, lane l adding members l, l + 64, ... in order and the
+ * lanes combined by a fixed butterfly: the same bits on every call, no atomics. */
+size_t ast_fof_workspace_bytes(size_t n);
+int ast_fof_max_passes(size_t n);
+int ast_fof_prepare(const void* pos_d, int pos_dtype, size_t n, void* work_d, size_t work_bytes, double* bounds_d,
+                    void* stream);
+int ast_fof_link(void* work_d, size_t work_bytes, size_t n, double boxsize, int cylinder, double b_perp, double b_para,
+                 int los, int single_cell, unsigned long long* links_d, void* stream);
+int ast_fof_compress(void* work_d, size_t work_bytes, size_t n, int* pending_d, int* passes_host, int* root_d,
+                     unsigned* size_d, void* stream);
+int ast_fof_relabel(const int* root_d, const int* table_d, size_t n, int* labels_d, void* stream);
+int ast_fof_features(const void* pos_d, int pos_dtype, const void* vel_d, int vel_dtype, const void* weights_d,
+                     int weights_dtype, size_t n, const int* members_d, const long long* offsets_d,
+                     const long long* first_d, size_t ngroups, double boxsize, double* cm_d, double* cmv_d,
+                     double* weight_d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
