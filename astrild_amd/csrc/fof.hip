@@ -377,7 +377,6 @@ extern "C" int ast_fof_compress(void* work_d, size_t work_bytes, size_t n, int* 
     int* parent = (int*)((char*)work_d + L.part);
     const int bound = ast_fof_max_passes(n);
     AST_CHECK_HIP(hipMemsetAsync(pending_d, 0, sizeof(int) * (size_t)bound, s));
-    AST_CHECK_HIP(hipMemsetAsync(size_d, 0, sizeof(unsigned) * n, s));
     const unsigned grid = ast::stream_grid(n, 256);
     *passes_host = 0;
     bool done = false;
@@ -396,8 +395,9 @@ extern "C" int ast_fof_compress(void* work_d, size_t work_bytes, size_t n, int* 
     if (!done) {
         ast::set_error("%s: parents not resolved after %d passes (n %zu): the parent array is not a forest", __func__,
                        bound, n);
-        return AST_ERR_LIMIT;
+        return AST_ERR_LIMIT;                    // root_d and size_d are untouched
     }
+    AST_CHECK_HIP(hipMemsetAsync(size_d, 0, sizeof(unsigned) * n, s));
     AST_PROF("fof_sizes", s);
     fof_sizes_kernel<<<grid, 256, 0, s>>>(parent, n, root_d, size_d);
     AST_CHECK_LAUNCH();

@@ -1260,8 +1260,8 @@ int ast_watershed_edges(const void* img_d, int dtype, const int* labels_d, int n
  * ast_fof_compress resolves the forest by pointer jumping, at most ast_fof_max_passes(n) = ceil(log2 n) + 1 passes (0:
  * n out of range); pending_d: that many int32 of device scratch; *passes_host = the passes taken.  SYNCHRONOUS (one
  * 4-byte read-back per pass); AST_ERR_LIMIT when the bound did not suffice, which no output of ast_fof_link can
- * cause.  Then root_d[i] (int32) = the smallest index of i's group and size_d[r] (uint32, n entries, zeroed by the
- * call) = the members of the group whose smallest index is r, 0 elsewhere.  n >= 1.
+ * cause (a parent array that is not a forest; root_d and size_d are then left untouched).  Then root_d[i] (int32) =
+ * the smallest index of i's group and size_d[r] (uint32, n entries, zeroed by the call) = the members of the group whose smallest index is r, 0 elsewhere.  n >= 1.
  * ast_fof_relabel: labels_d[i] = table_d[root_d[i]] (int32, n entries each).
  * ast_fof_features: for group g < ngroups with members members_d[offsets_d[g] .. offsets_d[g + 1]) (int32 particle
  * indices; offsets int64) and first_d[g] (int64) its reference particle: s_i = pos_i - pos[first], with boxsize > 0

@@ -28,15 +28,17 @@ class Plan(dict):
     __getattr__ = dict.__getitem__
 
 
-def plan_box(lo, hi, n, reach, single=False, margins=True, rounding=np.floor):
+def plan_box(lo, hi, n, reach, single=False, margins=True, rounding=np.floor, cap=None):
     """grid_box_plan for the bounding box [lo, hi] of n objects, op by op in float64: (dims, inv_cs, steps).
-    ``margins=False`` and ``rounding=np.ceil`` are the wrong planners of the sensitivity tests."""
+    ``cap``: the most cells the grid may have; None: the pair finders' min(n, MAX_CELLS) (a finder with a cap of its
+    own, such as fof.hip's fof_plan_cap, passes it).  ``margins=False`` and ``rounding=np.ceil`` are the wrong planners
+    of the sensitivity tests."""
     lo, hi = np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64)
     ext = hi - lo
     amax = np.float64(0.0)
     for a in range(3):
         amax = max(amax, max(abs(lo[a]), abs(hi[a])))
-    cap = float(1 if n < 1 else min(n, MAX_CELLS))
+    cap = float(1 if n < 1 else min(n, MAX_CELLS)) if cap is None else float(cap)
     dims = np.ones(3, dtype=np.int64)
     steps = 0
     if not single:
@@ -61,11 +63,11 @@ def plan_box(lo, hi, n, reach, single=False, margins=True, rounding=np.floor):
     return dims, inv_cs, steps
 
 
-def plan(pos, reach, single=False, **variant):
-    """grid_box_plan and grid_box_cell of cell_grid.h for a catalogue, op by op in float64."""
+def plan(pos, reach, single=False, cap=None, **variant):
+    """grid_box_plan and grid_box_cell of cell_grid.h for a catalogue, op by op in float64; ``cap`` as in plan_box."""
     pos = np.asarray(pos, dtype=np.float64)
     lo, hi = pos.min(axis=0), pos.max(axis=0)
-    dims, inv_cs, steps = plan_box(lo, hi, len(pos), reach, single, **variant)
+    dims, inv_cs, steps = plan_box(lo, hi, len(pos), reach, single, cap=cap, **variant)
     v = (pos - lo) * inv_cs
     v = np.where(v >= 0.0, v, 0.0)
     v = np.minimum(v, (dims - 1).astype(np.float64))
