@@ -1728,6 +1728,8 @@ static int rows_r2c_impl(const void* in, void* out, int dtype, size_t n, size_t 
     AST_CHECK_ARG(in != nullptr && out != nullptr && in != out && nrows >= 1);
     AST_CHECK_ARG(ast_fft_tile_supported(dtype, n));
     AST_CHECK_ARG(in_pitch >= n && in_pitch % 2 == 0 && out_pitch >= n / 2 + 1);
+    // rows_r2c_kernel reads the real rows - and the halo records - as float2: 8-byte aligned rows (the pitch is even)
+    AST_CHECK_ARG(((uintptr_t)in & 7) == 0 && ((uintptr_t)rec & 7) == 0 && ((uintptr_t)out & 7) == 0);
     const float2* tw = g_tw.get((int)n);
     if (!tw) { ast::set_error("ast_fft_tile_rows_r2c: twiddle table allocation failed"); return AST_ERR_HIP; }
     hipStream_t s = ast::as_stream(stream);
@@ -1927,6 +1929,9 @@ static int power_3d_impl(const void* grid, void* scratch, size_t scratch_bytes, 
     const double kf_rule = binning == AST_BIN_FLOAT64 ? 2.0 * M_PI / boxsize : 0.0;
     AST_CHECK_ARG(ast_fft_tile_supported(dtype, n));
     AST_CHECK_ARG(scratch_bytes >= ast_fft_tile_power_scratch_bytes(n));
+    // the z pass reads the grid's rows as float2 (refused here, before the low-k channel is queued); the scratch is cut
+    // into float2 / double2 areas at multiples of 256 bytes
+    AST_CHECK_ARG(((uintptr_t)grid & 7) == 0 && ((uintptr_t)rec & 7) == 0 && ((uintptr_t)scratch & 15) == 0);
     const size_t nz = n / 2 + 1, nzp = (nz + 15) / 16 * 16;
     float2* spec = (float2*)scratch;
     float2* disc = (float2*)((char*)scratch + n * n * nzp * sizeof(float2));
@@ -2097,6 +2102,7 @@ extern "C" int ast_fft_tile_c2r_3d(const void* spec, void* work, void* out, int 
     AST_CHECK_ARG(spec != nullptr && work != nullptr && out != nullptr && spec != work && work != out);
     AST_CHECK_ARG(ast_fft_tile_supported(dtype, n));
     AST_CHECK_ARG(m_lo >= 0 && (m_hi == 0 || m_hi > m_lo));
+    AST_CHECK_ARG(((uintptr_t)out & 15) == 0);                      // rows_c2r_kernel stores the real rows 16 bytes at a time
     const float2* tw = g_tw.get((int)n);
     if (!tw) { ast::set_error("ast_fft_tile_c2r_3d: twiddle table allocation failed"); return AST_ERR_HIP; }
     hipStream_t s = ast::as_stream(stream);
@@ -2142,6 +2148,7 @@ extern "C" int ast_fft_tile_c2r_3d_batch(const void* spec, void* const* works, v
         const int j = i < count ? i : count - 1;                  // (unused slots repeat the last shell)
         AST_CHECK_ARG(works[j] != nullptr && works[j] != spec);
         AST_CHECK_ARG(!(passes & 2) || (outs[j] != nullptr && works[j] != outs[j]));       // (no z pass: no output needed)
+        AST_CHECK_ARG(!(passes & 2) || ((uintptr_t)outs[j] & 15) == 0);                    // 16-byte stores of the real rows
         AST_CHECK_ARG(m_lo[j] >= 0 && m_hi[j] > m_lo[j]);
         sb.work[i] = (float2*)works[j];
         sb.lo2[i] = (long long)m_lo[j] * m_lo[j];

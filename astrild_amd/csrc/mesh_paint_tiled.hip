@@ -2705,6 +2705,7 @@ static int paint_tiled_impl(int window, int dtype, const void* pos, const void* 
     AST_CHECK_ARG(nmesh > 0 && boxsize > 0.0);
     AST_CHECK_ARG(x_start >= 0 && x_start < nmesh && nx_alloc > 0 && nx_alloc <= nmesh);
     AST_CHECK_ARG(grid != nullptr);
+    AST_CHECK_ARG(((uintptr_t)grid & 15) == 0);            // column_fold_kernel walks the grid's lines 16 bytes at a time
     AST_CHECK_ARG(np < 0xffffffffull - 64);
     if (np == 0) {
         if ((flags & AST_PAINT_OVERWRITE) && (sel.stage == AST_PAINT_STAGE_ALL || sel.stage == AST_PAINT_STAGE_GROUP))

@@ -10,6 +10,7 @@ import contextlib
 import ctypes as ct
 import itertools
 import os
+import warnings
 
 import numpy as np
 import torch
@@ -44,8 +45,24 @@ def as_device(a, dtype=None):
         t = a.to(device=device(), dtype=dtype or a.dtype)
     else:
         arr = np.ascontiguousarray(a)
-        t = torch.from_numpy(arr).to(device=device(), dtype=dtype)
+        if arr.flags.writeable:
+            t = torch.from_numpy(arr).to(device=device(), dtype=dtype)
+        else:                                 # a read-only array (a memory map): only copied from, torch's warning is moot
+            with warnings.catch_warnings():
+                warnings.filterwarnings("ignore", message="The given NumPy array is not writable")
+                t = torch.from_numpy(arr).to(device=device(), dtype=dtype)
     return t.contiguous()
+
+
+def dense(t, align=1):
+    """``t`` itself when it is contiguous and its first byte lies on a multiple of ``align`` bytes; otherwise a
+    contiguous copy in a fresh allocation (the caching allocator's blocks start on a multiple of 512 bytes).  The ONE
+    place where a wrapper fits a caller's tensor to a C entry that reads it flat or demands an alignment (DESIGN.md,
+    Input layouts): an aligned, contiguous tensor passes through without a kernel and without an allocation.  Only for
+    tensors the call reads; what it writes in place is checked with an assert instead."""
+    if t is None or (t.is_contiguous() and t.data_ptr() % align == 0):
+        return t
+    return t.clone(memory_format=torch.contiguous_format)
 
 
 def upload_planes(arrays, dtype=torch.float64, flat=True):
@@ -176,6 +193,7 @@ def total_mass(mass, npart):
     """Sum of the particle masses in double, fixed order (``npart`` for unit masses)."""
     if mass is None:
         return float(npart)
+    mass = dense(mass)
     out = torch.empty(1 + _lib.SUM_PARTS, dtype=torch.float64, device=mass.device)
     check(_lib.lib().ast_sum(ptr(mass), real_code(mass), mass.numel(), ptr(out), stream()), "ast_sum")
     return float(out[0].item())
@@ -210,6 +228,7 @@ def sample_is_unordered(pos, nmesh, boxsize, shift=0.0, windows=256, fraction=Fa
         return False
     n = int(nmesh)
     if pos.is_cuda:                                    # one small kernel + a 4-byte fetch (the torch ops below: 0.25 ms)
+        pos = dense(pos)
         cnt = torch.empty(1, dtype=torch.int32, device=pos.device)
         check(_lib.lib().ast_paint_order_probe(ptr(pos), real_code(pos), npart, n, float(boxsize), float(shift), int(windows),
                                                ptr(cnt), stream()), "ast_paint_order_probe")
@@ -236,6 +255,7 @@ def probe_input(pos, nmesh, boxsize, shift=0.0, windows=256):
     if cbytes == 0 or npart < 64:
         return None
     ntiles = cbytes // 4
+    pos = dense(pos)
     samples = min(npart, max(65536, 8 * ntiles))
     counts = torch.empty(cbytes, dtype=torch.uint8, device=pos.device)
     out = torch.zeros(3, dtype=torch.int64, device=pos.device)       # [overflow, max tile, groupable runs (low 4 bytes)]
@@ -652,8 +672,10 @@ def r2c(field, out=None, engine="auto"):
     """pmesh-normalised forward transform: ``rfftn(field) / Ng``.
 
     engine "tile": the hand-written three-pass LDS FFT (fp32 cubes of side 256/512/1024, fp64 cubes of side 128 ... 2048);
-    "rocfft": the rocFFT 3D R2C plan; "auto": tile when supported."""
+    "rocfft": the rocFFT 3D R2C plan; "auto": tile when supported.  A field that does not start on a multiple of 16
+    bytes (a view into a larger buffer) is transformed from an aligned copy: every engine reads the real rows as pairs."""
     assert field.is_cuda and field.dim() == 3 and field.is_contiguous()
+    field = dense(field, 16)
     n0, n1, n2 = field.shape
     code = real_code(field)
     if out is None:
@@ -824,6 +846,7 @@ def fftpower_2d(field1, boxsize, field2=None, Nmu=5, los=2, poles=(0, 2, 4), bin
     along box axis ``los``: r2c, then the (k, mu) / Legendre binning of the half spectrum (ast_power_bin_2d).  fp32
     grids are transformed in double, as in the non-fused branch of :func:`fftpower_1d` and for its reason."""
     Nmu, los, poles = check_fftpower_2d_args(Nmu, los, poles)
+    field1, field2 = dense(field1), dense(field2)
     n = field1.shape[0]
     assert tuple(field1.shape) == (n, n, n) and n % 2 == 0
     if field1.dtype == torch.float32:
@@ -877,12 +900,12 @@ def catalog_power_2d(pos1, mass1, nmesh, boxsize, window="tsc", interlaced=True,
     Nmu, los, poles = check_fftpower_2d_args(Nmu, los, poles)
     n = int(nmesh)
     if vel1 is not None:
-        pos1 = rsd_shift(pos1, vel1, boxsize, los, rsd_factor)
+        pos1 = rsd_shift(dense(pos1), dense(vel1), boxsize, los, rsd_factor)
     c1, sn = catalog_mesh_complex(pos1, mass1, n, boxsize, window, interlaced, compensated)
     c2 = None
     if pos2 is not None:
         if vel2 is not None:
-            pos2 = rsd_shift(pos2, vel2, boxsize, los, rsd_factor)
+            pos2 = rsd_shift(dense(pos2), dense(vel2), boxsize, los, rsd_factor)
         c2, _ = catalog_mesh_complex(pos2, mass2, n, boxsize, window, interlaced, compensated)
         sn = 0.0
     return finish_power_2d(*power_bin_2d(c1, c2, n, boxsize, Nmu, los, poles), poles=poles, shotnoise=sn)
@@ -925,6 +948,7 @@ def power_sums_fused(field, boxsize, psum=None, mean=0.0, halo=None, lowk=True, 
     and keeps fp32 round-off from scaling with the mean density (pass total_mass/Ng).
     ``lowk``: the five lowest shells come from double-precision DFT sums of the modes |m_i| <= 5 (one more read
     of the grid): the fp32 transform's round-off floor would otherwise cap them at ~2e-6 / |m|^2."""
+    field = dense(field, 16)                  # (the z pass reads the rows as pairs: ast_fft_tile_power_3d refuses less than 8)
     n = field.shape[0]
     L = _lib.lib()
     key = (torch.cuda.current_device(), n)
@@ -982,6 +1006,7 @@ def power_sums_fused64(field, boxsize, psum=None, binning=None, halo=None, mean=
     grid's ``mean`` given (0.0 for a grid that holds rho - mean), single-precision passes of their own
     (ast_fft32_big_power_3d)."""
     import os
+    field = dense(field, 16)                  # (the C entries refuse a grid off 16 bytes, 8 for fp32)
     n = field.shape[0]
     L = _lib.lib()
     if psum is None:
@@ -1029,6 +1054,7 @@ def paint_power_1d(pos, mass, nmesh, boxsize, window="cic", scale=1.0, binning=N
     pos_scale: the positions are in units of 1 / pos_scale box units (``pos * pos_scale`` is what the reference paints,
     stats_subfind.py:121-122: kpc -> Mpc/h): folded into the cell lookup - the catalogue is painted as it was read."""
     n = int(nmesh)
+    pos, mass = dense(pos), dense(mass)
     paint_box = float(boxsize) / float(pos_scale)
     # which tiled variant (None: a catalogue too sparse for the tiles - global atomics, then the plain transform)
     tiled = auto_paint_method(pos.shape[0], n, n, window) if n % 32 == 0 else "direct"
@@ -1057,6 +1083,7 @@ def paint_power_1d(pos, mass, nmesh, boxsize, window="cic", scale=1.0, binning=N
 def fftpower_1d(field1, boxsize, field2=None, fused=True, binning=None):
     """``FFTPower(first, mode="1d", kmin=2*pi/L[, second])`` for in-memory grids
     (nbodykit call sites: power_spectrum_3d.py:189-224, stats_subfind.py:142-150)."""
+    field1, field2 = dense(field1), dense(field2)
     n = field1.shape[0]
     assert tuple(field1.shape) == (n, n, n) and n % 2 == 0
     if fused and field2 is None and fused_power_supported(field1):
@@ -1103,6 +1130,7 @@ def catalog_mesh_complex(pos, mass, nmesh, boxsize, window="tsc", interlaced=Tru
     transformed with pmesh's 1/Ng convention, interlaced with a second paint shifted by half a cell and divided
     by the window.  Returns (half spectrum, shotnoise = L^3 sum w^2 / (sum w)^2)."""
     n = int(nmesh)
+    pos, mass = dense(pos), dense(mass)
     wsum = total_mass(mass, pos.shape[0])
     scale = float(n) ** 3 / wsum
     c1 = r2c(paint(pos, mass, n, boxsize, window, scale=scale))
@@ -1135,8 +1163,10 @@ def c2r(spec, shape, out=None):
     the input spectrum is used as scratch)."""
     n0, n1, n2 = shape
     code = _CPLX[spec.dtype]
+    assert spec.is_cuda and spec.is_contiguous()
     if out is None:
         out = torch.empty(shape, dtype=_TO_REAL[spec.dtype], device=spec.device)
+    assert out.is_contiguous()
     fft_plan(_lib.FFT_C2R, code, (n0, n1, n2), 1, 1.0, False).execute(spec, out)
     return out
 
@@ -1206,6 +1236,7 @@ def shell_filter(spec, nmesh, m_lo, m_hi, out=None, i0=None, i1=None, dtype=None
     if out is None:
         cd = spec.dtype if spec is not None else dtype
         out = torch.empty((i0[1], i1[1], n // 2 + 1), dtype=cd, device=device())
+    assert (spec is None or spec.is_contiguous()) and out.is_contiguous()
     check(_lib.lib().ast_shell_filter(ptr(spec), ptr(out), _CPLX[out.dtype], n, int(m_lo), int(m_hi),
                                       int(i0[0]), int(i0[1]), int(i1[0]), int(i1[1]), stream()),
           "ast_shell_filter")
@@ -1213,6 +1244,7 @@ def shell_filter(spec, nmesh, m_lo, m_hi, out=None, i0=None, i1=None, dtype=None
 
 
 def triple_product_sum(a, b, c):
+    a, b, c = dense(a), dense(b), dense(c)
     out = torch.zeros(1, dtype=torch.float64, device=a.device)
     check(_lib.lib().ast_triple_product_sum(ptr(a), ptr(b), ptr(c), real_code(a), a.numel(), ptr(out), stream()),
           "ast_triple_product_sum")

@@ -12,7 +12,7 @@ import torch
 
 from . import _lib
 from ._lib import F64, check
-from .device import as_device, device, ptr, real_code, stream, stream_key
+from .device import as_device, dense, device, ptr, real_code, stream, stream_key
 
 
 # ------------------------------------------------------------------ a-7 stack
@@ -76,6 +76,7 @@ def convert_code_to_phy_units(quantity, t):
         div = C_LIGHT_KMS ** 3
     else:
         return t
+    assert t.is_contiguous()
     check(_lib.lib().ast_divide(ptr(t), real_code(t), t.numel(), div, stream()), "ast_divide")
     return t
 
@@ -107,7 +108,7 @@ class LensPlan(_Plan):
 
     def alphas(self, kappa):
         assert kappa.is_cuda and kappa.dtype == torch.float64 and kappa.numel() == self.nc ** 2
-        kappa = kappa.contiguous()
+        kappa = dense(kappa, 16)                  # (ast_lens_rows_forward reads the rows 16 bytes at a time)
         a1, a2 = torch.empty_like(kappa), torch.empty_like(kappa)
         check(_lib.lib().ast_kappa_to_alphas(self.handle, ptr(kappa), ptr(a1), ptr(a2), stream()),
               "ast_kappa_to_alphas")
@@ -115,7 +116,7 @@ class LensPlan(_Plan):
 
     def phi(self, kappa):
         assert kappa.is_cuda and kappa.dtype == torch.float64 and kappa.numel() == self.nc ** 2
-        kappa = kappa.contiguous()
+        kappa = dense(kappa, 16)                  # (ast_lens_rows_forward reads the rows 16 bytes at a time)
         out = torch.empty_like(kappa)
         check(_lib.lib().ast_kappa_to_phi(self.handle, ptr(kappa), ptr(out), stream()), "ast_kappa_to_phi")
         return out
@@ -134,8 +135,11 @@ class SmoothPlan(_Plan):
         kernel with scipy's "mirror" boundary (the prefilter of skimage.transform.resize)."""
         assert img.is_cuda and img.dtype == torch.float64 and img.numel() == self.npix ** 2 and img.is_contiguous()
         mode = {"gaussianFFT": 0, "gaussian": 1, "gaussian_mirror": 2}[kind]
-        check(_lib.lib().ast_gaussian_smooth(self.handle, ptr(img), float(sigma_px), mode, stream()),
+        work = dense(img, 16)                     # (the periodic route hands the map to rocFFT's real transform)
+        check(_lib.lib().ast_gaussian_smooth(self.handle, ptr(work), float(sigma_px), mode, stream()),
               "ast_gaussian_smooth")
+        if work is not img:
+            img.copy_(work)
         return img
 
 
@@ -207,6 +211,7 @@ def deflection_to_shear(alpha1, alpha2, h):
 
 
 def minmax(t):
+    t = dense(t)
     out = torch.empty(2, dtype=torch.float64, device=t.device)
     check(_lib.lib().ast_minmax(ptr(t), real_code(t), t.numel(), ptr(out), stream()), "ast_minmax")
     lo, hi = out.cpu().numpy()
@@ -220,6 +225,7 @@ class PendingHistogram:
 
     def __init__(self, t, nbins, density=False):
         self.nbins, self.density = int(nbins), density
+        t = dense(t)
         buf = torch.zeros(self.nbins + 2, dtype=torch.int64, device=t.device)
         check(_lib.lib().ast_histogram_auto(ptr(t), real_code(t), t.numel(), self.nbins, ptr(buf), ptr(buf[self.nbins:]),
                                             stream()), "ast_histogram_auto")
@@ -251,6 +257,7 @@ def histogram(t, nbins, range=None, density=False):
     lo, hi = float(range[0]), float(range[1])
     if lo == hi:
         lo, hi = lo - 0.5, hi + 0.5
+    t = dense(t)
     counts = torch.zeros(nbins, dtype=torch.int64, device=t.device)
     check(_lib.lib().ast_histogram(ptr(t), real_code(t), t.numel(), lo, hi, nbins, ptr(counts), stream()),
           "ast_histogram")
@@ -264,6 +271,7 @@ def histogram(t, nbins, range=None, density=False):
 def order_statistics(t, ks):
     """Exact k-th smallest elements (0-based) of a device tensor - radix select on the GPU (ast_order_statistics)."""
     ks = [int(k) for k in ks]
+    t = dense(t)
     karr = (ct.c_size_t * len(ks))(*ks)
     out = (ct.c_double * len(ks))()
     scratch = torch.empty(2048, dtype=torch.int64, device=t.device)
@@ -331,7 +339,7 @@ def flat_power_spectrum(img, angle_deg, l_edges, img2=None):
     t = as_device(np.ascontiguousarray(img, dtype=np.float64)) if not isinstance(img, torch.Tensor) else img
     n = t.shape[0]
     assert t.dim() == 2 and t.shape[1] == n and t.dtype == torch.float64
-    ft1 = _rfft2(t.contiguous())
+    ft1 = _rfft2(dense(t, 16))
     ft2 = None if img2 is None else _rfft2(as_device(np.ascontiguousarray(img2, dtype=np.float64)))
     angle = np.deg2rad(angle_deg)
     edges = as_device(l_edges)
@@ -354,7 +362,7 @@ def flat_bispectrum_equilateral(img, angle_deg, l_edges):
     nb = len(l_edges) - 1
     t = as_device(np.ascontiguousarray(img, dtype=np.float64)) if not isinstance(img, torch.Tensor) else img
     n = t.shape[0]
-    ft = _rfft2(t.contiguous())
+    ft = _rfft2(dense(t, 16))
     ring = torch.empty_like(ft)
     field = torch.empty((n, n), dtype=torch.float64, device=t.device)
     angle = float(np.deg2rad(angle_deg))
@@ -374,7 +382,9 @@ def flat_bispectrum_equilateral(img, angle_deg, l_edges):
 
 
 def add(a, b, out=None):
+    a, b = dense(a), dense(b)
     out = torch.empty_like(a) if out is None else out
+    assert out.is_contiguous()
     check(_lib.lib().ast_add(ptr(a), ptr(b), ptr(out), real_code(a), a.numel(), stream()), "ast_add")
     return out
 
@@ -475,6 +485,8 @@ def nfw_paint(halo_cat, extent, direction, suppress, suppression_R, npix, signal
 
 def add_patch(limg, simg, cen_pix):
     """limg[y, x] += simg, clipped at the boundary (SkyUtils.add_patch_to_map, sky_utils.py:140-173)."""
+    assert limg.is_contiguous()
+    simg = dense(simg)
     check(_lib.lib().ast_add_patch(ptr(limg), limg.shape[0], ptr(simg), simg.shape[0], int(cen_pix[0]),
                                    int(cen_pix[1]), stream()), "ast_add_patch")
     return limg

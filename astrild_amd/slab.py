@@ -131,6 +131,8 @@ class HipSlabOps:
 
     def fft2d_planes(self, planes, out):
         from ._lib import check, lib
+        planes = self.dev.dense(planes, 16)      # (the z pass reads the real rows as pairs: DESIGN.md, Input layouts)
+        assert out.is_contiguous()
         nloc, n1, n2 = planes.shape
         code = self.dev.real_code(planes)
         if n1 == n2 and self._tile_ok(code, n1):
@@ -177,6 +179,7 @@ class HipSlabOps:
         (piece s of `packed`) and the rank's own piece into ``self_dst`` (its place in the receive block).
         lowz: (nplanes * n * 7) complex128 that receives the low-k channel's z sums of these planes from the z pass."""
         from ._lib import check, lib
+        planes = self.dev.dense(planes, 16)
         nloc, n1, n2 = planes.shape
         code = self.dev.real_code(planes)
         nz, pitch = n2 // 2 + 1, spec.shape[-1]
@@ -216,6 +219,7 @@ class HipSlabOps:
         """z rows of the planes into `spec`, then the k_y pass storing in the disc layout: part q's rows into
         packed[npl * cumS[q] : npl * (cumS[q] + S[q])] (what goes to rank q), the rank's own part into self_dst."""
         from ._lib import check, lib
+        planes = self.dev.dense(planes, 16)
         nloc, n1, n2 = planes.shape
         code = self.dev.real_code(planes)
         pitch = spec.shape[-1]
@@ -259,6 +263,7 @@ class HipSlabOps:
     def pack(self, spec, out, parts):
         from ._lib import check, lib
         n0, n1, n2 = spec.shape
+        assert spec.is_contiguous() and out.is_contiguous()
         check(lib().ast_slab_pack(self.dev.ptr(spec), self.dev.ptr(out), 0 if spec.dtype == torch.complex64 else 1,
                                   n0, n1, n2, parts, self.dev.stream()), "ast_slab_pack")
         return out
@@ -266,6 +271,7 @@ class HipSlabOps:
     def fft1d_axis0(self, block, scale):
         from ._lib import check, lib
         n0, n1, n2 = block.shape
+        assert block.is_contiguous()
         code = 0 if block.dtype == torch.complex64 else 1
         if self._tile_ok(code, n0):
             check(lib().ast_fft_tile_c2c(self.dev.ptr(block), code, n0, n1 * n2, n1 * n2, 1, 0, scale,
@@ -283,6 +289,7 @@ class HipSlabOps:
         back to HBM.  psum is overwritten with the block's shell sums (shells below first_bin left at zero)."""
         from ._lib import check, lib
         n0, nloc, pitch = block.shape
+        assert block.is_contiguous()
         key = (n, nloc)
         if getattr(self, "_bp_key", None) != key:
             self._bp_key = key
@@ -305,6 +312,7 @@ class HipSlabOps:
 
     def route_count(self, pos, n, boxsize, window, parts):
         from ._lib import WIN, check, lib
+        pos = self.dev.dense(pos)
         counts = torch.zeros(parts, dtype=torch.int64, device=self.device)
         check(lib().ast_route_count(self.dev.ptr(pos), self.dev.real_code(pos), pos.shape[0], n, float(boxsize),
                                     WIN[window.lower()], parts, self.dev.ptr(counts), self.dev.stream()), "ast_route_count")
@@ -312,6 +320,7 @@ class HipSlabOps:
 
     def route_scatter(self, pos, mass, n, boxsize, window, parts, counts):
         from ._lib import WIN, check, lib
+        pos, mass = self.dev.dense(pos), self.dev.dense(mass)
         cursor = torch.cumsum(counts, 0) - counts                  # exclusive prefix sums (P values)
         out_pos = torch.empty_like(pos)
         out_mass = None if mass is None else torch.empty_like(mass)

@@ -232,7 +232,12 @@ class Case:
     spectra whose own test compares two GPU routes with that tolerance, or whose oracle that test already holds the
     default-stream result to: what is asked here is that the stream changes nothing beyond the order of atomic additions.
     ``host_syncs`` / ``sync_line``: the wrapper reads a device value on the host, and where.
-    ``check(*inputs)``: the argument validator the inputs - and the decoys - must pass."""
+    ``check(*inputs)``: the argument validator the inputs - and the decoys - must pass.
+    For tests/input_layouts.py: ``mutates`` - the indices of the inputs the call is documented to write; ``refuses`` -
+    {input index: variant names}, the COMPLETE list of re-layouts of an input the call may refuse because the wrapper
+    asserts a contiguous tensor ("offset" never: a contiguous tensor of the right dtype is valid input everywhere);
+    ``refused_by`` - the functions (named as in ``covers``, private helpers of device.py included) whose source holds
+    that ``is_contiguous`` check."""
     name: str
     covers: tuple
     make: object
@@ -246,8 +251,14 @@ class Case:
     host_inputs: bool = False
     check: object = None
     env: dict = dataclasses.field(default_factory=dict)
+    mutates: tuple = ()
+    refuses: dict = dataclasses.field(default_factory=dict)
+    refused_by: tuple = ()
 
 
+#: what a contiguity assert refuses of a 1-D or 3-D input, and of a square map or an (N, 3) table
+_NC, _NCT = frozenset({"strided"}), frozenset({"strided", "transposed"})
+_PAINT_REFUSES = dict(refuses={0: _NCT, 1: _NC}, refused_by=("_check_paint_tensors",))
 CASES = []
 
 
@@ -296,26 +307,27 @@ for _dtype in (np.float32, np.float64):
         case(name=f"paint_direct_{_id}", covers=("paint",), make=_two(_particles(_dtype)), check=_check_particles,
              call=lambda dev, lens, p, m, w=_window: dev.paint(p, m, N_MESH, L_BOX, w, method="direct"),
              compare=(PAINT_TOL[_dtype],) * 2, tol_from="tests/test_gpu_mesh.py::test_paint_random_particles_with_mass",
-             oracle=_paint_oracle(_window), host_syncs=True, sync_line="paint: nd = int(dropped.item())")
+             oracle=_paint_oracle(_window), host_syncs=True, sync_line="paint: nd = int(dropped.item())", **_PAINT_REFUSES)
         for _method in ("tiled", "tiled2"):
             case(name=f"paint_{_method}_{_id}", covers=("paint",), make=_two(_particles(_dtype)), check=_check_particles,
                  call=lambda dev, lens, p, m, w=_window, me=_method: dev.paint(p, m, N_MESH, L_BOX, w, method=me,
                                                                                 accumulate=False),
-                 host_syncs=True, sync_line="_max_abs: float(lo_hi.abs().max()); paint: st.cpu().tolist(), dropped.item()")
+                 host_syncs=True, sync_line="_max_abs: float(lo_hi.abs().max()); paint: st.cpu().tolist(), dropped.item()",
+                 **_PAINT_REFUSES)
 case(name="paint_tiled_unchecked", covers=("paint",), make=_two(_particles(np.float32, masses=False)),
      check=_check_particles,
      call=lambda dev, lens, p, m: dev.paint(p, None, N_MESH, L_BOX, "cic", method="tiled", accumulate=False,
-                                            check_dropped=False))
+                                            check_dropped=False), **_PAINT_REFUSES)
 case(name="paint_direct_unchecked", covers=("paint",), make=_two(_particles(np.float32, masses=False)),
      check=_check_particles,
      call=lambda dev, lens, p, m: dev.paint(p, None, N_MESH, L_BOX, "tsc", method="direct", check_dropped=False),
      compare=(PAINT_TOL[np.float32],) * 2, tol_from="tests/test_gpu_mesh.py::test_paint_random_particles_with_mass",
-     oracle=_paint_oracle("tsc"))
+     oracle=_paint_oracle("tsc"), **_PAINT_REFUSES)
 case(name="paint_accumulate_tiled", covers=("paint",), make=_two(_particles(np.float64)), check=_check_particles,
      call=lambda dev, lens, p, m: dev.paint(p, m, N_MESH, L_BOX, "cic", method="tiled",
                                             out=torch.zeros((N_MESH,) * 3, dtype=p.dtype, device=p.device)),
      compare=(PAINT_TOL[np.float64],) * 2, tol_from="tests/test_gpu_mesh.py::test_paint_random_particles_with_mass",
-     oracle=_paint_oracle("cic"), host_syncs=True, sync_line="paint: nd = int(dropped.item())")
+     oracle=_paint_oracle("cic"), host_syncs=True, sync_line="paint: nd = int(dropped.item())", **_PAINT_REFUSES)
 
 
 def _lattice(npside, nmesh, seed, dtype):
@@ -343,7 +355,7 @@ def _staged_paint(dev, lens, pos, mass):
 
 case(name="staged_paint", covers=("StagedPaint.group", "StagedPaint.walk", "StagedPaint.fold"),
      make=_two(_particles(np.float32)), check=_check_particles, call=_staged_paint,
-     host_syncs=True, sync_line="StagedPaint.__init__: _max_abs(mass); check(): int(self.dropped.item())")
+     host_syncs=True, sync_line="StagedPaint.__init__: _max_abs(mass); check(): int(self.dropped.item())", **_PAINT_REFUSES)
 
 
 def _xsorted_particles(seed):
@@ -353,7 +365,7 @@ def _xsorted_particles(seed):
 case(name="paint_xsorted_two_streams", covers=("paint",), make=_two(_xsorted_particles), check=_check_particles,
      env={"AST_PAINT_XSTREAMS": "2", "AST_PAINT_XCHUNK_MB": "1"},
      call=lambda dev, lens, p, m: dev.paint(p, None, 256, L_BOX, "cic", method="tiled", accumulate=False, hint="xsorted",
-                                            check_dropped=False))
+                                            check_dropped=False), **_PAINT_REFUSES)
 
 
 def _defer_fold(dev, lens, p, m):
@@ -364,7 +376,8 @@ def _defer_fold(dev, lens, p, m):
 
 case(name="paint_defer_fold_halo_f64", covers=("paint", "power_sums_fused64"),
      make=_two(lambda seed: _lattice(64, 128, seed, np.float64)),
-     check=_check_particles, call=_defer_fold, compare=(1e-11, 0.0), tol_from="tests/test_gpu_fft_tile.py: psum of power_sums_fused64 against power_bin_1d, two GPU routes, rtol 1e-11, no atol")
+     check=_check_particles, call=_defer_fold, compare=(1e-11, 0.0), tol_from="tests/test_gpu_fft_tile.py: psum of power_sums_fused64 against power_bin_1d, two GPU routes, rtol 1e-11, no atol",
+     **_PAINT_REFUSES)
 
 
 def _unit_cube(seed):
@@ -397,7 +410,8 @@ def _check_in_box(box):
 
 case(name="rsd_shift", covers=("rsd_shift",), make=_two(_pos_vel(5001, 500.0, 3000.0)), check=_check_in_box(500.0),
      call=lambda dev, lens, p, v: dev.rsd_shift(p, v, 500.0, los=2),
-     host_syncs=True, sync_line="rsd_shift: float(v) for v in torch.aminmax(res[:, los])")
+     host_syncs=True, sync_line="rsd_shift: float(v) for v in torch.aminmax(res[:, los])",
+     refuses={0: _NCT, 1: _NCT}, refused_by=("rsd_shift",))
 case(name="synth_particles", covers=("synth_lattice_particles", "synth_clustered_particles"), make=lambda: ([], []),
      call=lambda dev, lens: (dev.synth_lattice_particles(32, 64, L_BOX, seed=5, dtype=torch.float32),
                              dev.synth_lattice_particles(32, 64, L_BOX, seed=5, shuffle=True, dtype=torch.float64),
@@ -446,7 +460,7 @@ def _fused_halo(dev, lens, p, m):
 
 
 case(name="power_sums_fused_halo_256", covers=("power_sums_fused", "paint"), make=_two(_xsorted_particles),
-     check=_check_particles, call=_fused_halo)
+     check=_check_particles, call=_fused_halo, **_PAINT_REFUSES)
 case(name="power_sums_fused64_f64_128", covers=("power_sums_fused64",), make=_two(_field(128, np.float64)),
      check=_check_finite, call=lambda dev, lens, f: dev.power_sums_fused64(f, L_BOX), compare=(1e-11, 0.0),
      tol_from="tests/test_gpu_fft_tile.py: psum of power_sums_fused64 against power_bin_1d, two GPU routes, rtol 1e-11, no atol")
@@ -470,7 +484,8 @@ case(name="power_bin_1d_2d_device", covers=("power_bin_1d", "power_bin_2d", "r2c
      check=_check_finite,
      call=lambda dev, lens, f: (dev.power_bin_1d(dev.r2c(f), None, 64, L_BOX),
                                 dev.power_bin_2d(dev.r2c(f), None, 64, L_BOX, Nmu=5, los=2, poles=(0, 2, 4))),
-     compare=(1e-12, 1e-12), tol_from="tests/test_gpu_fftpower2d.py: rtol 1e-12, and for the multipoles (signed sums) an atol of 1e-12 of the monopole; here of the leaf's own largest value, which is no larger")
+     compare=(1e-12, 1e-12), tol_from="tests/test_gpu_fftpower2d.py: rtol 1e-12, and for the multipoles (signed sums) an atol of 1e-12 of the monopole; here of the leaf's own largest value, which is no larger",
+     refuses={0: _NC}, refused_by=("r2c",))
 
 
 def _catalogue(seed):
@@ -490,7 +505,8 @@ case(name="catalog_power_2d_64", covers=("catalog_power_2d", "rsd_shift"), make=
      host_syncs=True, sync_line="rsd_shift: torch.aminmax; total_mass: out[0].item(); finish_power_2d: t.cpu().numpy()")
 case(name="lowk_modes_shell_sums", covers=("lowk_modes", "lowk_shell_sums"), make=_two(_field(256, np.float32)),
      check=_check_finite,
-     call=lambda dev, lens, f: (lambda modes: (modes, dev.lowk_shell_sums(modes, 256, L_BOX)))(dev.lowk_modes(f, 256)))
+     call=lambda dev, lens, f: (lambda modes: (modes, dev.lowk_shell_sums(modes, 256, L_BOX)))(dev.lowk_modes(f, 256)),
+     refuses={0: _NC}, refused_by=("lowk_modes",))
 
 
 # ---- transforms
@@ -506,22 +522,24 @@ def _half_spectrum(n, cdtype, seed):
 
 
 case(name="r2c_rocfft_64", covers=("r2c", "fft_plan", "FFTPlan.execute"), make=_two(_field(64, np.float32)),
-     check=_check_finite, call=lambda dev, lens, f: dev.r2c(f, engine="rocfft"))
+     check=_check_finite, call=lambda dev, lens, f: dev.r2c(f, engine="rocfft"), refuses={0: _NC}, refused_by=("r2c",))
 case(name="r2c_tile_256", covers=("r2c",), make=_two(_field(256, np.float32)), check=_check_finite,
-     call=lambda dev, lens, f: dev.r2c(f, engine="tile"))
+     call=lambda dev, lens, f: dev.r2c(f, engine="tile"), refuses={0: _NC}, refused_by=("r2c",))
 case(name="r2c_fft64_128", covers=("r2c",), make=_two(_field(128, np.float64)), check=_check_finite,
-     call=lambda dev, lens, f: dev.r2c(f))
+     call=lambda dev, lens, f: dev.r2c(f), refuses={0: _NC}, refused_by=("r2c",))
 case(name="c2r_rocfft_64", covers=("c2r", "fft_plan", "FFTPlan.execute"), make=_two(_spectrum(64, np.complex128)),
      check=_check_finite, call=lambda dev, lens, s: dev.c2r(s.clone(), (64, 64, 64)))
 case(name="c2r_tile_256", covers=("c2r_tile",), make=_two(_spectrum(256, np.complex64)), check=_check_finite,
-     call=lambda dev, lens, s: (dev.c2r_tile(s), dev.c2r_tile(s, m_lo=3, m_hi=9)))
+     call=lambda dev, lens, s: (dev.c2r_tile(s), dev.c2r_tile(s, m_lo=3, m_hi=9)), refuses={0: _NC}, refused_by=("c2r_tile",))
 case(name="c2r_tile_batch_256", covers=("c2r_tile_batch", "tile_work_pitch"), make=_two(_spectrum(256, np.complex64)),
      check=_check_finite,
      call=lambda dev, lens, s: dev.c2r_tile_batch(
          s, [(1, 4), (4, 9), (9, 20)],
-         [torch.empty((256, 256, dev.tile_work_pitch(256)), dtype=torch.complex64, device=s.device) for _ in range(3)]))
+         [torch.empty((256, 256, dev.tile_work_pitch(256)), dtype=torch.complex64, device=s.device) for _ in range(3)]),
+     refuses={0: _NC}, refused_by=("c2r_tile_batch",))
 case(name="shell_filter_64", covers=("shell_filter",), make=_two(_spectrum(64, np.complex128)), check=_check_finite,
-     call=lambda dev, lens, s: (dev.shell_filter(s, 64, 3, 9), dev.shell_filter(None, 64, 3, 9, dtype=torch.complex128)))
+     call=lambda dev, lens, s: (dev.shell_filter(s, 64, 3, 9), dev.shell_filter(None, 64, 3, 9, dtype=torch.complex128)),
+     refuses={0: _NC}, refused_by=("shell_filter",))
 
 
 def _three_fields(seed):
@@ -532,12 +550,13 @@ def _three_fields(seed):
 case(name="triple_product_sums_64", covers=("triple_product_sums",), make=_two(_three_fields),
      check=_check_finite,      # (repeated calls are torch.equal in tests/test_gpu_bispectrum_kernels.py)
      call=lambda dev, lens, a, b, c: dev.triple_product_sums({0: a, 1: b, 2: c}, [(0, 1, 2), (0, 0, 1), (2, 2, 2)]),
-     host_syncs=True, sync_line="triple_product_sums: torch.tensor(...).to(device()) - a pageable upload waits for the stream")
+     host_syncs=True, sync_line="triple_product_sums: torch.tensor(...).to(device()) - a pageable upload waits for the stream",
+     refuses={0: _NC, 1: _NC, 2: _NC}, refused_by=("triple_product_sums",))
 case(name="bispectrum_32", covers=("bispectrum",), make=_two(_field(32, np.float64)), check=_check_finite,
      call=lambda dev, lens, f: (lambda r: (r["B"], r["ntri"]))(dev.bispectrum(f, L_BOX, [1, 4, 8, 12],
                                                                               [(0, 0, 0), (0, 1, 1), (1, 1, 2), (0, 1, 2)])),
      compare=(1e-8, 1e-9), tol_from="tests/test_gpu_api.py::test_bispectrum_3d_vs_oracle: rtol 1e-8, atol 1e-9 of the largest |B|",
-     host_syncs=True, sync_line="bispectrum: triple_product_sums(...).cpu().numpy()")
+     host_syncs=True, sync_line="bispectrum: triple_product_sums(...).cpu().numpy()", refuses={0: _NC}, refused_by=("r2c",))
 
 
 # ---- grid operations
@@ -560,7 +579,8 @@ case(name="vector_magnitude", covers=("vector_magnitude",), make=_two(_vector_gr
      check=_check_finite, call=lambda dev, lens, v: dev.vector_magnitude(v))
 case(name="spectral_divergence_16", covers=("spectral_divergence",),
      make=_two(lambda seed: [_spectrum(16, np.complex128)(seed + k)[0] for k in range(3)]), check=_check_finite,
-     call=lambda dev, lens, a, b, c: dev.spectral_divergence(a, b, c, 16, L_BOX))
+     call=lambda dev, lens, a, b, c: dev.spectral_divergence(a, b, c, 16, L_BOX),
+     refuses={0: _NC, 1: _NC, 2: _NC}, refused_by=("spectral_divergence",))
 case(name="velocity_divergence_power_32", covers=("velocity_divergence_power",),
      make=_two(_vector_grid((32, 32, 32), np.float64)), check=_check_finite,
      call=lambda dev, lens, v: dev.velocity_divergence_power(v, L_BOX), compare=(1e-12, 0.0),
@@ -575,7 +595,7 @@ def _planes(seed):
 
 _WNUM, _WDEN = np.linspace(0.5, 1.5, 5), np.linspace(2.0, 1.0, 5)
 case(name="kappa_stack_weighted", covers=("lensing.kappa_stack",), make=_two(_planes), check=_check_finite,
-     call=lambda dev, lens, p: lens.kappa_stack(p, _WNUM, _WDEN))
+     call=lambda dev, lens, p: lens.kappa_stack(p, _WNUM, _WDEN), refuses={0: _NC}, refused_by=("lensing.kappa_stack",))
 case(name="convert_units_add", covers=("lensing.convert_code_to_phy_units", "lensing.add"), make=_two(_planes),
      check=_check_finite,
      call=lambda dev, lens, p: lens.add(lens.convert_code_to_phy_units("kappa_2", p[0].clone()), p[1]))
@@ -603,7 +623,9 @@ for _npix in (64, 256):
     for _kind, _sigma in (("gaussianFFT", 3.0), ("gaussianFFT", 1.0), ("gaussian", 1.2), ("gaussian_mirror", 1.5)):
         case(name=f"smooth_plan_{_kind}_{_sigma}_{_npix}", covers=("lensing.SmoothPlan.gaussian",), make=_two(_kappa(_npix)),
              check=_check_finite,
-             call=lambda dev, lens, k, n=_npix, kd=_kind, sg=_sigma: _explicit_plan(lens, "SmoothPlan", n).gaussian(k.clone(), sg, kd))
+             call=lambda dev, lens, k, n=_npix, kd=_kind, sg=_sigma: _explicit_plan(lens, "SmoothPlan", n).gaussian(k.clone(), sg, kd),
+             # (in place: the clone of a strided view is contiguous, the clone of a transposed map keeps its strides)
+             refuses={0: frozenset({"transposed"})}, refused_by=("lensing.SmoothPlan.gaussian",))
 case(name="resize_antialiased_96_24", covers=("lensing.resize_antialiased", "lensing.smooth_plan"), make=_two(_kappa(96)),
      check=_check_finite, call=lambda dev, lens, k: lens.resize_antialiased(k, 24))
 case(name="histogram_minmax", covers=("lensing.histogram", "lensing.minmax", "lensing.PendingHistogram.__init__"),
@@ -616,7 +638,7 @@ case(name="order_statistics_percentile", covers=("lensing.order_statistics", "le
      host_syncs=True, sync_line="ast_order_statistics writes its results into a host array (ctypes out)")
 case(name="peak_find_129", covers=("lensing.peak_find",), make=_two(_kappa(129)), check=_check_finite,
      call=lambda dev, lens, k: lens.peak_find(k),
-     host_syncs=True, sync_line="peak_find: n = int(count.item())")
+     host_syncs=True, sync_line="peak_find: n = int(count.item())", refuses={0: _NCT}, refused_by=("lensing.peak_find",))
 _L_EDGES = np.linspace(200.0, 4000.0, 9)
 case(name="flat_power_spectrum_64", covers=("lensing.flat_power_spectrum",), make=_two(_kappa(64)), check=_check_finite,
      call=lambda dev, lens, k: lens.flat_power_spectrum(k, 3.0, _L_EDGES),
@@ -655,7 +677,9 @@ def _patch(seed):
 case(name="add_patch_shear_37", covers=("lensing.add_patch", "lensing.deflection_to_shear"), make=_two(_patch),
      check=_check_finite,
      call=lambda dev, lens, big, small, other: (lens.add_patch(big.clone(), small, (3, 35)),
-                                               lens.deflection_to_shear(big, other, 0.01)))
+                                               lens.deflection_to_shear(big, other, 0.01)),
+     # (add_patch writes its first argument: the clone of a transposed map keeps its strides)
+     refuses={0: frozenset({"transposed"})}, refused_by=("lensing.add_patch",))
 
 
 def _filters(dev, lens, img, _small, _other):
