@@ -225,6 +225,7 @@ SIGNATURES = {
     "ast_fof_compress": (_i, [_vp, _sz, _sz, _vp, ct.POINTER(_i), _vp, _vp, _vp]),
     "ast_fof_relabel": (_i, [_vp, _vp, _sz, _vp, _vp]),
     "ast_fof_features": (_i, [_vp, _i, _vp, _i, _vp, _i, _sz, _vp, _vp, _vp, _sz, _d, _vp, _vp, _vp, _vp]),
+    "ast_readout": (_i, [_i, _i, _i, _vp, _i, _i, _vp, _sz, _d, _d, _vp, _vp]),
 }
 
 _lib = None

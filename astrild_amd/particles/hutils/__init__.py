@@ -6,4 +6,5 @@ from .pair_velocity_box import (los_pvd_vs_rp, mean_los_velocity_vs_rp, mean_rad
 from .tpcf import (TPCF, rp_pi_tpcf, rp_pi_tpcf_jackknife, s_mu_tpcf, tpcf_jackknife, tpcf_multipole,  # noqa: F401
                    tpcf_r, wp, wp_from_xi, wp_jackknife)
 from .fof import FOF, FoFGroups, check_fof_args, fof_features, fof_groups  # noqa: F401
+from .readout import check_readout_args, density_at, readout  # noqa: F401
 from .map_transform import MapTransform, MapTransformWarning  # noqa: F401

@@ -1283,6 +1283,25 @@ int ast_fof_features(const void* pos_d, int pos_dtype, const void* vel_d, int ve
                      const long long* first_d, size_t ngroups, double boxsize, double* cm_d, double* cmv_d,
                      double* weight_d, void* stream);
 
+/* ------------------------------------------------------------- mesh readout: grid -> particles
+ * A periodic grid field evaluated at positions with the NGP / CIC / TSC window.  Replaces pmesh
+ * RealField.readout(pos, resampler=), the adjoint of the ParticleMesh.paint that ast_paint replaces
+ * (particles/hutils/stats_subfind.py:130-131); the reference never calls it - it takes grids to the host instead.
+ *   field_d: the WHOLE grid, nmesh^3 * ncomp elements of field_dtype, C order, the ncomp (1 .. 4) components of a cell
+ *            interleaved on the last axis: (n, n, n) or (n, n, n, ncomp).
+ *   pos_d:   (np, 3) AoS of pos_dtype (independent of field_dtype), box units; any real value wraps periodically.
+ *   out_d:   (np, ncomp) of field_dtype; every element is overwritten.  No workspace.
+ * Per particle and axis s = fma((double)x, nmesh / boxsize, shift_cells); base cell and offset, weights and stencil
+ * as in ast_paint (weights evaluated in field_dtype).  Then, weights widened to double, per component c
+ *   acc = 0.0;  for a (x): for b (y): { wab = wx[a] * wy[b];  for cz (z): acc += (wab * wz[cz]) * (double)field[..] }
+ *   out[p][c] = (field_dtype)acc
+ * in exactly this order, without fused multiply-adds: the same bits on every call and for every launch geometry.
+ * A NaN or infinite coordinate gives NaN in every component of that particle; no coordinate of any bit pattern
+ * makes the call read outside field_d (base cells are clamped to [0, nmesh - 1]).
+ * np == 0: AST_OK without a launch. */
+int ast_readout(int window, int field_dtype, int pos_dtype, const void* field_d, int nmesh, int ncomp, const void* pos_d,
+                size_t np, double boxsize, double shift_cells, void* out_d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
