@@ -153,8 +153,19 @@ class FFTPlan:
 _plan_cache = {}
 
 
+def stream_key():
+    """(device, handle of the current stream): what the hidden plan caches (``fft_plan`` here, lensing's two) add to their
+    keys.  A plan owns ONE set of device buffers, so two streams must never share one; keyed this way every stream gets
+    its own (Streams)."""
+    return torch.cuda.current_device(), int(torch.cuda.current_stream().cuda_stream)
+
+
 def fft_plan(kind, dtype_code, lengths, batch=1, scale=1.0, inplace=False, strided=None):
-    key = (torch.cuda.current_device(), kind, dtype_code, tuple(lengths), batch, scale, inplace, strided)
+    """The cached rocFFT plan of the CURRENT stream for these parameters.  A plan owns one work buffer (as large as the
+    grid for a 3-D transform), so the key holds the stream: two streams that ask for the same transform get a plan and
+    a work buffer each and may run side by side; a caller that stays on one stream holds exactly the one plan it held
+    before.  Plans of streams that no longer exist stay until :func:`clear_plan_cache`."""
+    key = (*stream_key(), kind, dtype_code, tuple(lengths), batch, scale, inplace, strided)
     p = _plan_cache.get(key)
     if p is None:
         p = _plan_cache[key] = FFTPlan(kind, dtype_code, lengths, batch, scale, inplace, strided)
@@ -162,13 +173,9 @@ def fft_plan(kind, dtype_code, lengths, batch=1, scale=1.0, inplace=False, strid
 
 
 def clear_plan_cache():
+    """Drops every cached plan, those of streams that are gone included (their work buffers are freed with hipFree,
+    which waits for the device: work still queued in a plan finishes first)."""
     _plan_cache.clear()
-
-
-def stream_key():
-    """(device, handle of the current stream): what lensing's hidden plan caches add to their keys.  A plan owns ONE set
-    of device buffers, so two streams must never share one; keyed this way every stream gets its own (Streams)."""
-    return torch.cuda.current_device(), int(torch.cuda.current_stream().cuda_stream)
 
 
 # ------------------------------------------------------------ mass assignment
@@ -709,26 +716,47 @@ def _bin_code(binning):
     return _lib.BIN[binning or DEFAULT_BINNING]
 
 
+def _geom_cached(key, fill):
+    """The cached geometry tensors of ``key`` as COPIES on the current stream; ``fill()`` computes them, on the current
+    stream, when the key is new.  The entry is (tensors, stream of the fill, event recorded behind the fill): a hit
+    under another stream waits for that event first - the fill may still be queued - and tells the allocator about the
+    new reader (Streams).  What the caller gets is its own: the cached tensors never leave this function, so
+    a caller's ``ksum /= nmodes`` cannot reach the next spectrum of that size (two copies of nmesh/2-1 numbers each)."""
+    cur = torch.cuda.current_stream()
+    hit = _geom_cache.get(key)
+    if hit is None:
+        tensors = fill()
+        filled = torch.cuda.Event()
+        filled.record(cur)
+        hit = _geom_cache[key] = (tensors, cur, filled)
+    elif hit[1] != cur:
+        cur.wait_event(hit[2])
+        for t in hit[0]:
+            t.record_stream(cur)
+    return tuple(t.clone() for t in hit[0])
+
+
 def shell_geometry(nmesh, boxsize, i0=None, i1=None, binning=None):
-    """(sum w|k|, sum w) per shell of a spectrum block — data independent, cached."""
+    """(sum w|k|, sum w) per shell of a spectrum block — data independent, cached; the caller's own copies."""
     n = int(nmesh)
     i0 = (0, n) if i0 is None else tuple(i0)
     i1 = (0, n) if i1 is None else tuple(i1)
     key = (torch.cuda.current_device(), n, float(boxsize), i0, i1, _bin_code(binning))
-    hit = _geom_cache.get(key)
-    if hit is None:
+
+    def fill():
         nb = n // 2 - 1
         ksum = torch.zeros(nb, dtype=torch.float64, device=device())
         nmodes = torch.zeros(nb, dtype=torch.int64, device=device())
         check(_lib.lib().ast_power_bin_1d(None, None, F64, n, float(boxsize), int(i0[0]), int(i0[1]),
                                           int(i1[0]), int(i1[1]), ptr(ksum), None, ptr(nmodes), _bin_code(binning), stream()),
               "ast_power_bin_1d[geometry]")
-        hit = _geom_cache[key] = (ksum, nmodes)
-    return hit
+        return ksum, nmodes
+    return _geom_cached(key, fill)
 
 
 def power_bin_1d(spec1, spec2, nmesh, boxsize, i0=None, i1=None, psum=None, binning=None):
-    """Shell sums (ksum, psum, nmodes) of a block of the half spectrum (device tensors)."""
+    """Shell sums (ksum, psum, nmodes) of a block of the half spectrum (device tensors; ksum and nmodes are copies of
+    the cached geometry: the caller's own)."""
     n = int(nmesh)
     nb = n // 2 - 1
     i0 = (0, n) if i0 is None else tuple(i0)
@@ -781,14 +809,14 @@ def _poles_arg(poles):
 
 def shell_geometry_2d(nmesh, boxsize, Nmu, los, i0=None, i1=None, binning=None):
     """(sum w|k|, sum w mu, sum w) per (shell, mu bin) of a spectrum block, (nmesh/2-1, Nmu) each - data independent,
-    cached."""
+    cached; the caller's own copies."""
     Nmu, los, _ = check_fftpower_2d_args(Nmu, los, ())
     n = int(nmesh)
     i0 = (0, n) if i0 is None else tuple(i0)
     i1 = (0, n) if i1 is None else tuple(i1)
     key = (torch.cuda.current_device(), n, float(boxsize), i0, i1, _bin_code(binning), Nmu, los)
-    hit = _geom_cache.get(key)
-    if hit is None:
+
+    def fill():
         nb = n // 2 - 1
         ksum = torch.zeros((nb, Nmu), dtype=torch.float64, device=device())
         musum = torch.zeros((nb, Nmu), dtype=torch.float64, device=device())
@@ -796,15 +824,16 @@ def shell_geometry_2d(nmesh, boxsize, Nmu, los, i0=None, i1=None, binning=None):
         check(_lib.lib().ast_power_bin_2d(None, None, F64, n, float(boxsize), int(i0[0]), int(i0[1]), int(i1[0]), int(i1[1]),
                                           los, Nmu, None, 0, ptr(ksum), ptr(musum), ptr(nmodes), None, None,
                                           _bin_code(binning), stream()), "ast_power_bin_2d[geometry]")
-        hit = _geom_cache[key] = (ksum, musum, nmodes)
-    return hit
+        return ksum, musum, nmodes
+    return _geom_cached(key, fill)
 
 
 def power_bin_2d(spec1, spec2, nmesh, boxsize, Nmu=5, los=2, poles=(0, 2, 4), i0=None, i1=None, psum=None, polesum=None,
                  binning=None):
     """Wedge and multipole sums (ksum, musum, psum, nmodes, polesum) of a block of the half spectrum (device tensors):
     the first four (nmesh/2-1, Nmu), polesum (len(poles), nmesh/2-1) without the factor 2l + 1 - see ast_power_bin_2d.
-    ``psum`` / ``polesum`` given: accumulated into (blocks and ranks add)."""
+    ``psum`` / ``polesum`` given: accumulated into (blocks and ranks add).  ksum, musum and nmodes are copies of the
+    cached geometry: the caller's own."""
     Nmu, los, poles = check_fftpower_2d_args(Nmu, los, poles)
     n = int(nmesh)
     nb = n // 2 - 1
@@ -947,7 +976,8 @@ def power_sums_fused(field, boxsize, psum=None, mean=0.0, halo=None, lowk=True, 
     ``mean`` is subtracted from the cells on load: it only touches the discarded DC mode
     and keeps fp32 round-off from scaling with the mean density (pass total_mass/Ng).
     ``lowk``: the five lowest shells come from double-precision DFT sums of the modes |m_i| <= 5 (one more read
-    of the grid): the fp32 transform's round-off floor would otherwise cap them at ~2e-6 / |m|^2."""
+    of the grid): the fp32 transform's round-off floor would otherwise cap them at ~2e-6 / |m|^2.
+    ksum and nmodes are copies of the cached geometry: the caller's own."""
     field = dense(field, 16)                  # (the z pass reads the rows as pairs: ast_fft_tile_power_3d refuses less than 8)
     n = field.shape[0]
     L = _lib.lib()
@@ -1004,7 +1034,7 @@ def power_sums_fused64(field, boxsize, psum=None, binning=None, halo=None, mean=
     double-precision passes (ast_fft64_power_3d): one pass per axis, the last one fused with the shell binning.  fp32 cubes
     of the sides the fp32 tile passes do not cover take the same passes, widened on load - or, at side 2048 and with the
     grid's ``mean`` given (0.0 for a grid that holds rho - mean), single-precision passes of their own
-    (ast_fft32_big_power_3d)."""
+    (ast_fft32_big_power_3d).  ksum and nmodes are copies of the cached geometry: the caller's own."""
     import os
     field = dense(field, 16)                  # (the C entries refuse a grid off 16 bytes, 8 for fp32)
     n = field.shape[0]

@@ -237,7 +237,16 @@ class Case:
     {input index: variant names}, the COMPLETE list of re-layouts of an input the call may refuse because the wrapper
     asserts a contiguous tensor ("offset" never: a contiguous tensor of the right dtype is valid input everywhere);
     ``refused_by`` - the functions (named as in ``covers``, private helpers of device.py included) whose source holds
-    that ``is_contiguous`` check."""
+    that ``is_contiguous`` check.
+    ``shares`` / ``shares_doc``: the outputs are NOT the caller's to overwrite - the reason is a sentence of the
+    docstring of the function ``shares_doc`` names (as in ``covers``) which says that the result is shared or owned by a
+    plan (tests/test_stream_order_cpu.py holds the field to that docstring).  Explicit plan objects only: no hidden cache
+    hands out its own memory.
+    ``geometry_leaves``: the leaves of the output (numbered as ``leaves`` yields them) that are the shell geometry's
+    float sums, for the cases that compare bitwise.  They are sums of float64 atomics: the same to the last bit while
+    the geometry stays cached, not between two fills (tests/input_layouts.py keeps one cache per case for that
+    reason).  A test that empties the cache between the reference and the call compares these leaves with
+    GEOMETRY_TOL, the tolerance the geometry's own test holds them to, and every other leaf as the case says."""
     name: str
     covers: tuple
     make: object
@@ -254,7 +263,14 @@ class Case:
     mutates: tuple = ()
     refuses: dict = dataclasses.field(default_factory=dict)
     refused_by: tuple = ()
+    shares: str = ""
+    shares_doc: str = ""
+    geometry_leaves: tuple = ()
 
+
+#: ksum of a refilled geometry cache against the one before: tests/test_gpu_fftpower2d.py holds the power_bin_1d / 2d
+#: sums to each other and to the oracle with rtol 1e-12, no atol
+GEOMETRY_TOL = (1e-12, 0.0)
 
 #: what a contiguity assert refuses of a 1-D or 3-D input, and of a square map or an (N, 3) table
 _NC, _NCT = frozenset({"strided"}), frozenset({"strided", "transposed"})
@@ -448,9 +464,9 @@ def _check_finite(*arrays):
 
 
 case(name="power_sums_fused_lowk_256", covers=("power_sums_fused", "shell_geometry"), make=_two(_field(256, np.float32)),
-     check=_check_finite, call=lambda dev, lens, f: dev.power_sums_fused(f, L_BOX, mean=1.0, lowk=True))
+     check=_check_finite, call=lambda dev, lens, f: dev.power_sums_fused(f, L_BOX, mean=1.0, lowk=True), geometry_leaves=(0,))
 case(name="power_sums_fused_nolowk_256", covers=("power_sums_fused",), make=_two(_field(256, np.float32)),
-     check=_check_finite, call=lambda dev, lens, f: dev.power_sums_fused(f, L_BOX, mean=1.0, lowk=False))
+     check=_check_finite, call=lambda dev, lens, f: dev.power_sums_fused(f, L_BOX, mean=1.0, lowk=False), geometry_leaves=(0,))
 
 
 def _fused_halo(dev, lens, p, m):
@@ -460,7 +476,7 @@ def _fused_halo(dev, lens, p, m):
 
 
 case(name="power_sums_fused_halo_256", covers=("power_sums_fused", "paint"), make=_two(_xsorted_particles),
-     check=_check_particles, call=_fused_halo, **_PAINT_REFUSES)
+     check=_check_particles, call=_fused_halo, geometry_leaves=(0,), **_PAINT_REFUSES)
 case(name="power_sums_fused64_f64_128", covers=("power_sums_fused64",), make=_two(_field(128, np.float64)),
      check=_check_finite, call=lambda dev, lens, f: dev.power_sums_fused64(f, L_BOX), compare=(1e-11, 0.0),
      tol_from="tests/test_gpu_fft_tile.py: psum of power_sums_fused64 against power_bin_1d, two GPU routes, rtol 1e-11, no atol")
@@ -468,10 +484,11 @@ case(name="power_sums_fused64_f32_128", covers=("power_sums_fused64",), make=_tw
      check=_check_finite, call=lambda dev, lens, f: dev.power_sums_fused64(f, L_BOX), compare=(1e-11, 0.0),
      tol_from="tests/test_gpu_fft_tile.py: psum of power_sums_fused64 against power_bin_1d, two GPU routes, rtol 1e-11, no atol")
 case(name="power_sums_fused64_big32_256", covers=("power_sums_fused64",), make=_two(_field(256, np.float32)),
-     check=_check_finite, call=lambda dev, lens, f: dev.power_sums_fused64(f, L_BOX, mean=1.0))
+     check=_check_finite, call=lambda dev, lens, f: dev.power_sums_fused64(f, L_BOX, mean=1.0), geometry_leaves=(0,))
 case(name="paint_power_1d_256", covers=("paint_power_1d",), make=_two(_xsorted_particles), check=_check_particles,
      call=lambda dev, lens, p, m: dev.paint_power_1d(p, None, 256, L_BOX, "cic"),
-     host_syncs=True, sync_line="paint -> total_mass / dropped.item(); finish_power: t.cpu().numpy()")
+     host_syncs=True, sync_line="paint -> total_mass / dropped.item(); finish_power: t.cpu().numpy()",
+     geometry_leaves=(0,))                                      # (the dict of finish_power: "k" = ksum / nmodes comes first)
 case(name="fftpower_1d_64", covers=("fftpower_1d", "power_bin_1d", "r2c"), make=_two(_field(64, np.float64)),
      check=_check_finite, call=lambda dev, lens, f: dev.fftpower_1d(f, L_BOX), compare=(1e-12, 0.0),
      tol_from="tests/test_gpu_fftpower2d.py: power_bin_1d / 2d sums against each other and the oracle, rtol 1e-12, no atol",
@@ -972,3 +989,97 @@ def environment(env):
         yield
     finally:
         mp.undo()
+
+
+# ------------------------------------------------------------------ the registry of hidden state
+KINDS = ("event", "per_stream", "built_synchronously", "host_only", "explicit_object")
+
+
+@dataclasses.dataclass
+class Hidden:
+    """One thing in the package that outlives a call and holds device memory, a plan, a stream or an event (DESIGN.md,
+    Streams, rule 2).  ``where``: the file, relative to the package; ``name``: the module attribute, or the C object.
+    ``kind``: how it is handed between streams -
+      "event"               an event on the entry, waited for by a foreign stream;
+      "per_stream"          keyed by device.stream_key() or by the caller's stream: every stream gets its own;
+      "built_synchronously" complete (hipMemcpy, or a fill followed by hipStreamSynchronize) before it is cached;
+      "host_only"           no device memory, no stream, no event: host values, mutexes, once-flags;
+      "explicit_object"     rule 3: not hidden, or used by one call at a time under a lock - the caller orders it.
+    ``filled_by``: Python - the function of the module whose source holds the hand-over (``wait_event`` for "event",
+    ``stream_key()`` for "per_stream"); C - the struct whose ``get`` fills a "built_synchronously" table.
+    ``clear``: ``clear(monkeypatch)`` makes it cold inside this process (undone with the monkeypatch), or None with
+    ``no_clear``, the reason."""
+    where: str
+    name: str
+    holds: str
+    kind: str
+    filled_by: str = ""
+    clear: object = None
+    no_clear: str = ""
+
+
+def _swap_for_empty(module, attr):
+    def clear(mp):
+        import importlib
+        mp.setattr(importlib.import_module(module), attr, {})
+    return clear
+
+
+_FRESH = "lives in the library, which has no entry that drops it: cold only in a fresh process"
+_HOST = "host state: nothing on the device to make cold"
+_ONCE = "a flag per device that an idempotent attribute call was made: " + _HOST
+
+HIDDEN_STATE = [
+    # ---- Python
+    Hidden("device.py", "_plan_cache", "rocFFT plans with one hipMalloc'ed work buffer each", "per_stream",
+           filled_by="fft_plan", clear=_swap_for_empty("astrild_amd.device", "_plan_cache")),
+    Hidden("device.py", "_geom_cache", "shell geometry (ksum, [musum,] nmodes), 1-D and 2-D, with the fill's stream and event",
+           "event", filled_by="_geom_cached", clear=_swap_for_empty("astrild_amd.device", "_geom_cache")),
+    Hidden("device.py", "_power_scratch", "the one scratch tensor of the fused power paths, with its last use's stream and event",
+           "event", filled_by="_power_scratch_for", clear=_swap_for_empty("astrild_amd.device", "_power_scratch")),
+    Hidden("device.py", "_tri_cache", "triangle counts of the bispectrum as numpy arrays and floats", "host_only",
+           clear=_swap_for_empty("astrild_amd.device", "_tri_cache")),
+    Hidden("lensing.py", "_lens_plans", "ONE resident LensPlan (kernel spectra, work buffers)", "per_stream",
+           filled_by="lens_plan", clear=_swap_for_empty("astrild_amd.lensing", "_lens_plans")),
+    Hidden("lensing.py", "_smooth_plans", "SmoothPlans (rocFFT plans, cached weights)", "per_stream",
+           filled_by="smooth_plan", clear=_swap_for_empty("astrild_amd.lensing", "_smooth_plans")),
+    # ---- C: tables
+    Hidden("csrc/fft_tile.hip", "g_tw", "fp32 twiddle tables per (device, N)", "built_synchronously",
+           filled_by="TwiddleCache", no_clear=_FRESH),
+    Hidden("csrc/fft_tile.hip", "g_edge", "float64-edge tables per (device, N, boxsize), at most four", "built_synchronously",
+           filled_by="EdgeFallCache", no_clear=_FRESH + "; a boxsize no other test uses reaches a cold entry"),
+    Hidden("csrc/fft_tile.hip", "g_disc", "disc layouts: host tables and their device copies", "built_synchronously",
+           filled_by="DiscCache", no_clear=_FRESH),
+    Hidden("csrc/fft_tile.hip", "g_lowk_lane", "lane factors of the fused low-k z sums per (device, N)", "built_synchronously",
+           filled_by="LowkLaneCache", no_clear=_FRESH),
+    Hidden("csrc/fft_tile.hip", "g_side", "low-k side stream and event pair per (device, caller stream)", "per_stream",
+           no_clear=_FRESH),
+    Hidden("csrc/lens_fft.hip", "g_tw", "float64 twiddle tables per (device, length)", "built_synchronously",
+           filled_by="TwCache", no_clear=_FRESH),
+    Hidden("csrc/lens_fft.hip", "g_tw32", "fp32 twiddle tables per (device, length)", "built_synchronously",
+           filled_by="TwCache32", no_clear=_FRESH),
+    # ---- C: plans, streams, communicators
+    Hidden("csrc/kappa.hip", "g_host_plan", "the lens plan of the libglsg-compatible host entries", "explicit_object",
+           no_clear=_FRESH + "; host_lens holds g_host_mutex, works on the null stream and ends with hipDeviceSynchronize"),
+    Hidden("csrc/kappa.hip", "g_host_mutex", "the lock of g_host_plan", "host_only", no_clear=_HOST),
+    Hidden("csrc/mesh_paint_tiled.hip", "pipes", "SidePipe per device: the x-sorted paint's side stream and events",
+           "explicit_object",
+           no_clear=_FRESH + "; a pipelined paint holds SidePipe::run, every walk waits for an event of the caller's stream "
+                             "and the caller's stream waits for the last walk"),
+    Hidden("csrc/mesh_paint_tiled.hip", "mu", "the lock of side_pipe's table", "host_only", no_clear=_HOST),
+    Hidden("csrc/mesh_paint_tiled.hip", "g_stamps", "device global: time stamps of the paint's profiling build", "explicit_object",
+           no_clear="written only by kernels compiled with the stamp macro on, read by the script that enables it"),
+    Hidden("csrc/mesh_paint_tiled.hip", "g_nstamp", "device global: the count beside g_stamps", "explicit_object",
+           no_clear="as g_stamps"),
+    Hidden("csrc/comm.hip", "g_rccl", "the dlopen'ed RCCL entry points", "host_only", no_clear=_HOST),
+    Hidden("csrc/comm.hip", "g_rccl_mu", "the lock of g_rccl", "host_only", no_clear=_HOST),
+    Hidden("csrc/fft_plan.hip", "g_setup_once", "rocfft_setup was called", "host_only", no_clear=_HOST),
+    Hidden("csrc/util.hip", "g_err", "the thread's last error message", "host_only", no_clear=_HOST),
+    Hidden("csrc/util.hip", "g_prof", "the profiler's records: a pair of events per launch site visit, on the launch stream",
+           "host_only", no_clear="ast_profile_report waits for every pair and drops them; off unless a script enables it"),
+    Hidden("csrc/util.hip", "g_prof_on", "the profiler's switch", "host_only", no_clear=_HOST),
+    Hidden("csrc/util.hip", "g_prof_mutex", "the lock of g_prof", "host_only", no_clear=_HOST),
+] + [Hidden("csrc/" + f, n, "PerDeviceOnce: the kernel's dynamic-LDS limit was raised on this device", "host_only", no_clear=_ONCE)
+     for f, n in (("fft_tile.hip", "attr_once"), ("pairwise_pdf.hip", "attr_once"), ("tpcf.hip", "attr_once"),
+                  ("power_bin.hip", "attr_once"), ("power_bin_2d.hip", "attr_once"), ("mesh_paint_tiled.hip", "attr_once"),
+                  ("kappa.hip", "y_once"), ("lens_fft.hip", "once"))]
