@@ -375,20 +375,13 @@ constexpr int MINPOP = 8;              // records with fewer particles would was
 #define GROUP_CAND 16, 8, 24, 0
 #endif
 constexpr int GROUP_ITERS = GROUP_ITERS_N;         // tiles that can get a record per 32-particle window
-// How phase 1 of tile_group_kernel decides and appends (perf switches like COL_U; 0 / 0 is the kernel as it was):
-//   GROUP_SCALAR_N      the window decisions - takers per half, MINPOP, members, strays, pending, the early exit - are
-//                       algebra on the two 32-bit words of the ballots, which the compiler keeps on the scalar unit; a lane
-//                       compares its key with the two candidates and reads its own bit of the finished masks, nothing else;
-//   GROUP_WAVE_LISTS_N  each of the four waves appends to its own slice of the LDS lists with the fill counts in scalar
-//                       registers (no returning LDS atomic in the loop); phases 2 and 4 walk the four slices as one list.
-#ifndef GROUP_SCALAR_N
-#define GROUP_SCALAR_N 1
-#endif
-#ifndef GROUP_WAVE_LISTS_N
-#define GROUP_WAVE_LISTS_N 1
-#endif
-#if GROUP_WAVE_LISTS_N
-// a wave looks at AGG_TRIPS * IDX_UNROLL slots of two windows per interval, and a window makes at most GROUP_ITERS records:
+// How phase 1 of tile_group_kernel decides and appends:
+//   * the window decisions - takers per half, MINPOP, members, strays, pending, the early exit - are made ONCE per wave, as
+//     algebra on the two 32-bit words of the ballots, which the compiler keeps on the scalar unit; a lane compares its key
+//     with the two candidates and reads its own bit of the finished masks, nothing else;
+//   * each of the four waves appends to its own slice of the LDS lists with the fill counts in scalar registers (no
+//     returning LDS atomic in the loop); phases 2 and 4 walk the four slices as one list (paint_group_lists.h).
+// A wave looks at AGG_TRIPS * IDX_UNROLL slots of two windows per interval, and a window makes at most GROUP_ITERS records:
 // the wave's record slice holds all of them and is never full
 constexpr uint32_t WREC_CAP = ast::wave_record_capacity(AGG_TRIPS * IDX_UNROLL, GROUP_ITERS);
 #ifndef WST_CAP_N
@@ -402,13 +395,10 @@ constexpr uint32_t WREC_CAP = ast::wave_record_capacity(AGG_TRIPS * IDX_UNROLL, 
 // {particle, tile} for phase 2 (one global atomic per stray, all in flight together: 3.13 -> 3.88 ms).
 constexpr uint32_t WST_CAP = WST_CAP_N;
 constexpr uint32_t LREC_CAP = 4 * WREC_CAP, LST_CAP = 4 * WST_CAP;
+// (512 records and 768 strays: lists of that size, shared by the waves, are what fitted the budget before the slices)
 #ifdef WST_CAP_IS_DEFAULT      // (a capacity from the command line is an experiment)
 static_assert(3 * LREC_CAP + 5 * LST_CAP <= 3 * 512 + 5 * 768 && 3 * LREC_CAP + 8 * LST_CAP <= 3 * 512 + 8 * 768,
               "the lists (3 words per record, 5 or 8 per stray) must not grow: 31 KB of LDS are five workgroups per CU at float32");
-#endif
-#else
-constexpr uint32_t LREC_CAP = 512;     // records parked in LDS per interval (128 windows x up to 3; rest: slow path)
-constexpr uint32_t LST_CAP = 768;      // strays parked in LDS per interval (the bench input has ~330)
 #endif
 struct GroupRec { uint32_t first, mask; };
 
@@ -442,13 +432,15 @@ __device__ __noinline__ void place_group_slow(uint32_t key, uint32_t a, uint32_t
 }
 
 // Phases of one interval of 4096 contiguous particles (one workgroup):
-//   1 trips    cell lookup, grouping by ballots; group records and strays (position, tile) are APPENDED to
-//              LDS lists - no table lookups here, and (GROUP_WAVE_LISTS_N) every wave to a slice of its own with the fill
-//              counts in scalar registers, so the loop carries no dependent LDS round trips at all;
-//   2 slots    one thread per list entry: tile -> table slot (CAS) and the entry's offset in the slot;
+//   1 trips    cell lookup, grouping by ballots (the decisions of a window once per wave, on the two ballot words); group
+//              records and strays (position, tile) are APPENDED to LDS lists - no table lookups here, and every wave to a
+//              slice of its own with the fill counts in scalar registers, so the loop carries no dependent LDS round trips
+//              at all; the counts reach LDS once, at the end of the phase;
+//   2 slots    one thread per list entry (the four slices as one list): tile -> table slot (CAS) and the entry's offset in
+//              the slot;
 //   3 reserve  one thread per used slot: ONE returning 64-bit global atomic per distinct tile;
 //   4 scatter  one thread per entry: 8-byte records and 16-byte stray copies to their final place.
-// A table slot taken by another tile, or a full LDS list, sends the entry through place_group_slow
+// A table slot taken by another tile, or a full stray slice, sends the entry through place_group_slow
 // (its global atomics are issued by independent threads, all in flight together).
 
 // One late particle (AST_PAINT_XSORTED: its tile row has been handed to the column walk already) goes to the overflow
@@ -475,27 +467,18 @@ tile_group_kernel(const T* __restrict__ pos, const T* __restrict__ mass, size_t 
     // strays: position, particle id, tile key (same conversion)
     __shared__ T lst_x[LST_CAP], lst_y[LST_CAP], lst_z[LST_CAP];
     __shared__ uint32_t lst_p[LST_CAP], lst_key[LST_CAP];
-#if GROUP_WAVE_LISTS_N
     // wave w owns the entries [w * WREC_CAP, (w + 1) * WREC_CAP) and [w * WST_CAP, (w + 1) * WST_CAP) of the lists; its fill
     // counts reach LDS once per interval, at the end of phase 1
     __shared__ uint32_t wave_nrec[4], wave_nst[4];
-#else
-    __shared__ uint32_t lrec_n, lst_n;
-#endif
     constexpr uint32_t DST_NONE = 0xffffffffu;
     FSTAMP_DECL;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int half = lane >> 5;
-#if GROUP_SCALAR_N || GROUP_WAVE_LISTS_N
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane(tid >> 6);      // in a scalar register
-#endif
     skey[tid] = SLOT_EMPTY;
     srun[tid] = 0;
     sstray[tid] = 0;
-#if !GROUP_WAVE_LISTS_N
-    if (tid == 0) { lst_n = 0; lrec_n = 0; }
-#endif
     __syncthreads();
     const size_t per_trip = 256 * IDX_UNROLL;
     const size_t per_interval = per_trip * AGG_TRIPS;
@@ -525,6 +508,30 @@ tile_group_kernel(const T* __restrict__ pos, const T* __restrict__ mass, size_t 
         const uint32_t old = atomicCAS(&skey[slot], SLOT_EMPTY, key);
         return (old == SLOT_EMPTY || old == key) ? (int)slot : -1;
     };
+    uint32_t wrec_n, wst_n;     // this wave's fill counts of an interval: uniform, advanced by the popcounts of the masks
+    // the lanes of the mask (str_hi, str_lo) are strays: they append themselves to the wave's slice of the stray list, at its
+    // fill count plus the count of stray lanes below them
+    auto append_strays = [&](uint32_t str_lo, uint32_t str_hi, uint32_t key, uint32_t p, T x, T y, T z) {
+        const unsigned long long sm = (unsigned long long)str_lo | ((unsigned long long)str_hi << 32);
+        if (sm) {                                                          // uniform
+            const uint32_t cnt = (uint32_t)__popc(str_lo) + (uint32_t)__popc(str_hi);
+            const uint32_t at = wst_n;
+            wst_n += cnt;
+            if (__builtin_amdgcn_inverse_ballot_w64(sm)) {
+                const uint32_t i = at + __builtin_amdgcn_mbcnt_hi(str_hi, __builtin_amdgcn_mbcnt_lo(str_lo, 0u));
+                if (i < WST_CAP) {
+                    const uint32_t k = wave * WST_CAP + i;
+                    lst_x[k] = x;
+                    lst_y[k] = y;
+                    lst_z[k] = z;
+                    lst_p[k] = p;
+                    lst_key[k] = key;
+                } else {
+                    slow(key, p, 0u);                                      // slice full (scattered input)
+                }
+            }
+        }
+    };
     static_assert(AGG_TRIPS % 2 == 0, "two register sets");
     T xa[IDX_UNROLL], ya[IDX_UNROLL], za[IDX_UNROLL], xb[IDX_UNROLL], yb[IDX_UNROLL], zb[IDX_UNROLL];
     // xcd_map: workgroup b runs on XCD b mod 8 (round-robin dispatch: observed, nothing depends on it for correctness); with
@@ -537,9 +544,7 @@ tile_group_kernel(const T* __restrict__ pos, const T* __restrict__ mass, size_t 
         const size_t p0 = p_begin + interval * per_interval;
         const bool full = p0 + per_interval <= np;
         const uint32_t p0_32 = (uint32_t)p0, left = (uint32_t)min(np - p0, per_interval);      // particle ids fit 32 bits (checked by the host)
-#if GROUP_WAVE_LISTS_N
-        uint32_t wrec_n = 0, wst_n = 0;     // this wave's fill counts: uniform, advanced by the popcounts of the masks
-#endif
+        wrec_n = wst_n = 0;
         auto process = [&](int trip, const T (&x)[IDX_UNROLL], const T (&y)[IDX_UNROLL], const T (&z)[IDX_UNROLL]) {
 #pragma unroll
             for (int u = 0; u < IDX_UNROLL; ++u) {
@@ -570,7 +575,6 @@ tile_group_kernel(const T* __restrict__ pos, const T* __restrict__ mass, size_t 
                 // three fixed lanes of the window (two v_readlane each, no cross-lane search): in a spatially
                 // coherent input nearly every window is one tile plus a few strays, and the first candidate
                 // settles it.  A candidate with fewer than MINPOP takers leaves them as strays.
-#if GROUP_SCALAR_N
                 // Everything about a window is the same for its 32 lanes, so it is computed ONCE per wave, on the lower and
                 // the upper word of the ballots (scalar selects and bit counts).  A candidate whose own lane is not pending
                 // any more (dead, or taken by an earlier candidate) shares its key with no pending lane: "& pend" is the
@@ -592,29 +596,15 @@ tile_group_kernel(const T* __restrict__ pos, const T* __restrict__ mass, size_t 
                     const uint32_t big_hi = ((uint32_t)__popc(m_hi) + (32u - MINPOP)) >> 5;
                     if (big_lo | big_hi) {                                         // uniform
                         const uint32_t nrec = big_lo + big_hi;
-#if GROUP_WAVE_LISTS_N
                         const uint32_t base = wave * WREC_CAP + wrec_n;            // (never full, see WREC_CAP)
                         wrec_n += nrec;
-#else
-                        uint32_t base = 0;
-                        if (lane == 0) base = atomicAdd(&lrec_n, nrec);
-                        base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-#endif
                         const unsigned long long writers = (unsigned long long)big_lo | ((unsigned long long)big_hi << 32);
                         if (__builtin_amdgcn_inverse_ballot_w64(writers)) {
                             const uint32_t k = base + (half ? big_lo : 0u);
                             const uint32_t rfirst = first_lo + (half ? 32u : 0u), rmask = half ? m_hi : m_lo, rkey = half ? k1 : k0;
-#if GROUP_WAVE_LISTS_N
-                            {
-#else
-                            if (k >= LREC_CAP) {
-                                slow(rkey, rfirst, rmask);
-                            } else {
-#endif
-                                lrec_first[k] = rfirst;
-                                lrec_mask[k] = rmask;
-                                lrec_key[k] = rkey;
-                            }
+                            lrec_first[k] = rfirst;
+                            lrec_mask[k] = rmask;
+                            lrec_key[k] = rkey;
                         }
                     }
                     str_lo |= m_lo & (big_lo - 1u);
@@ -625,111 +615,7 @@ tile_group_kernel(const T* __restrict__ pos, const T* __restrict__ mass, size_t 
                 }
                 str_lo |= pend_lo;
                 str_hi |= pend_hi;
-                // strays append themselves to the LDS list at the wave's base plus the count of stray lanes below them
-                const unsigned long long sm = (unsigned long long)str_lo | ((unsigned long long)str_hi << 32);
-                if (sm) {                                                          // uniform
-                    const uint32_t cnt = (uint32_t)__popc(str_lo) + (uint32_t)__popc(str_hi);
-#if GROUP_WAVE_LISTS_N
-                    const uint32_t at = wst_n;
-                    wst_n += cnt;
-                    constexpr uint32_t room = WST_CAP;
-                    const uint32_t slice = wave * WST_CAP;
-#else
-                    uint32_t at = 0;
-                    if (lane == 0) at = atomicAdd(&lst_n, cnt);
-                    at = (uint32_t)__builtin_amdgcn_readfirstlane((int)at);
-                    constexpr uint32_t room = LST_CAP, slice = 0;
-#endif
-                    if (__builtin_amdgcn_inverse_ballot_w64(sm)) {
-                        const uint32_t i = at + __builtin_amdgcn_mbcnt_hi(str_hi, __builtin_amdgcn_mbcnt_lo(str_lo, 0u));
-                        if (i < room) {
-                            const uint32_t k = slice + i;
-                            lst_x[k] = x[u];
-                            lst_y[k] = y[u];
-                            lst_z[k] = z[u];
-                            lst_p[k] = (uint32_t)p;
-                            lst_key[k] = key;
-                        } else {
-                            slow(key, (uint32_t)p, 0u);                            // slice full (scattered input)
-                        }
-                    }
-                }
-#else
-                bool pending = live, stray = false;
-#pragma unroll
-                for (int it = 0; it < GROUP_ITERS; ++it) {
-                    constexpr int cand[4] = {GROUP_CAND};
-                    const uint32_t k0 = (uint32_t)__builtin_amdgcn_readlane((int)key, cand[it]);
-                    const uint32_t k1 = (uint32_t)__builtin_amdgcn_readlane((int)key, cand[it] + 32);
-                    const bool match = pending && key == (half ? k1 : k0);
-                    const unsigned long long mb = __ballot(match);
-                    const uint32_t mlo = (uint32_t)mb, mhi = (uint32_t)(mb >> 32);
-                    const uint32_t mm = half ? mhi : mlo;
-                    const bool big = half ? __popc(mhi) >= MINPOP : __popc(mlo) >= MINPOP;
-#if GROUP_WAVE_LISTS_N
-                    const bool writer = big && match && (lane & 31) == __ffs((int)mm) - 1;       // the group's first lane
-                    const unsigned long long wb = __ballot(writer);
-                    if (writer) {
-                        const uint32_t k = wave * WREC_CAP + wrec_n + (half && (uint32_t)wb ? 1u : 0u);       // (never full)
-                        lrec_first[k] = (uint32_t)p - (uint32_t)(lane & 31);
-                        lrec_mask[k] = mm;
-                        lrec_key[k] = key;
-                    }
-                    wrec_n += (uint32_t)__popcll(wb);
-                    stray = stray || (match && !big);
-#else
-                    if (big) {
-                        if (match && (lane & 31) == __ffs((int)mm) - 1) {          // the group's first lane
-                            const uint32_t first = (uint32_t)p - (uint32_t)(lane & 31);
-                            const uint32_t k = atomicAdd(&lrec_n, 1u);
-                            if (k < LREC_CAP) {
-                                lrec_first[k] = first;
-                                lrec_mask[k] = mm;
-                                lrec_key[k] = key;
-                            } else {
-                                slow(key, first, mm);
-                            }
-                        }
-                    } else {
-                        stray = stray || match;
-                    }
-#endif
-                    pending = pending && !match;
-                    const unsigned long long pend = __ballot(pending);
-                    if (__popc((uint32_t)pend) < MINPOP && __popc((uint32_t)(pend >> 32)) < MINPOP) break;      // uniform
-                }
-                stray = stray || pending;
-                // strays append themselves to the LDS list: one atomic per wave (the first stray lane reserves
-                // for all of them)
-                const unsigned long long sm = __ballot(stray);
-                if (sm) {                                                      // uniform
-#if GROUP_WAVE_LISTS_N
-                    const uint32_t base = wst_n;
-                    wst_n += (uint32_t)__popcll(sm);
-                    constexpr uint32_t room = WST_CAP;
-                    const uint32_t slice = wave * WST_CAP;
-#else
-                    const int lead = __ffsll((long long)sm) - 1;
-                    uint32_t base = 0;
-                    if (lane == lead) base = atomicAdd(&lst_n, (uint32_t)__popcll(sm));
-                    base = (uint32_t)__builtin_amdgcn_readlane((int)base, lead);
-                    constexpr uint32_t room = LST_CAP, slice = 0;
-#endif
-                    if (stray) {
-                        const uint32_t i = base + (uint32_t)__popcll(sm & ((1ull << lane) - 1ull));
-                        const uint32_t k = slice + i;
-                        if (i < room) {
-                            lst_x[k] = x[u];
-                            lst_y[k] = y[u];
-                            lst_z[k] = z[u];
-                            lst_p[k] = (uint32_t)p;
-                            lst_key[k] = key;
-                        } else {
-                            slow(key, (uint32_t)p, 0u);                        // list full (scattered input)
-                        }
-                    }
-                }
-#endif
+                append_strays(str_lo, str_hi, key, p, x[u], y[u], z[u]);
             }
         };
         FSTAMP(1);
@@ -741,26 +627,18 @@ tile_group_kernel(const T* __restrict__ pos, const T* __restrict__ mass, size_t 
             process(trip + 1, xb, yb, zb);
         }
         FSTAMP(2);
-#if GROUP_WAVE_LISTS_N
         if (lane == 0) {
             wave_nrec[wave] = wrec_n;
             wave_nst[wave] = min(wst_n, WST_CAP);
         }
-#endif
         __syncthreads();
         FSTAMP(3);
         // phase 2: slots
-#if GROUP_WAVE_LISTS_N
         // the four slices as one list: entry e of all nr (ns) is entry e - (entries of the waves before) of its wave's slice
         const uint32_t r1 = wave_nrec[0], r2 = r1 + wave_nrec[1], r3 = r2 + wave_nrec[2], nr = r3 + wave_nrec[3];
         const uint32_t s1 = wave_nst[0], s2 = s1 + wave_nst[1], s3 = s2 + wave_nst[2], ns = s3 + wave_nst[3];
         auto rec_at = [&](uint32_t e) { return ast::slice_entry(e, r1, r2, r3, WREC_CAP); };
         auto stray_at = [&](uint32_t e) { return ast::slice_entry(e, s1, s2, s3, WST_CAP); };
-#else
-        const uint32_t nr = min(lrec_n, LREC_CAP), ns = min(lst_n, LST_CAP);
-        auto rec_at = [](uint32_t e) { return e; };
-        auto stray_at = [](uint32_t e) { return e; };
-#endif
         for (uint32_t e = tid; e < nr; e += 256) {
             const uint32_t k = rec_at(e);
             const uint32_t key = lrec_key[k];
@@ -814,9 +692,6 @@ tile_group_kernel(const T* __restrict__ pos, const T* __restrict__ mass, size_t 
         skey[tid] = SLOT_EMPTY;
         srun[tid] = 0;
         sstray[tid] = 0;
-#if !GROUP_WAVE_LISTS_N
-        if (tid == 0) { lst_n = 0; lrec_n = 0; }
-#endif
         __syncthreads();
         FSTAMP(9);
     }

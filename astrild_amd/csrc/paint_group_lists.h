@@ -1,4 +1,4 @@
-// The wave-private LDS lists of the paint's grouping kernel (mesh_paint_tiled.hip, GROUP_WAVE_LISTS_N): how many
+// The wave-private LDS lists of the paint's grouping kernel (mesh_paint_tiled.hip, tile_group_kernel): how many
 // entries a wave's slice holds, and where entry e of the four slices taken as ONE list lies.  Plain integer code,
 // compiled for the device by the kernel and for the host by tests/host/paint_group_lists_test.cpp.
 #pragma once

@@ -1,6 +1,6 @@
 """Site times of the tiled paint at the benchmark's configuration (1024^3 lattice, natural order, CIC, fp32, hint "ordered"),
 best and mean of `reps` paints, for ONE build of the library: run once per build, one process each
-(scripts/build_variants.sh <tag> -DGROUP_SCALAR_N=0 ...; ASTRILD_HIP_LIB=astrild_amd/libastrild_hip_<tag>.so).  Prints one JSON
+(scripts/build_variants.sh <tag> -DWST_CAP_N=160 ...; ASTRILD_HIP_LIB=astrild_amd/libastrild_hip_<tag>.so).  Prints one JSON
 line: the sites, the list statistics, and sum and sum of squares of the painted grid in float64 (equal between builds).
 usage: python scripts/perf_group_variants.py <tag> [reps=9]"""
 import json, os, sys

@@ -9,10 +9,11 @@ full of 0xFF bytes (tests/dirty_memory.py), and the repeats must give the same b
 overflow list (its deposits are float atomics, whose order varies).  Coordinates and masses are rounded to float32
 first, so one oracle grid serves both dtypes.
 
-The grouping as it was stays selectable by build macros only (``-DGROUP_SCALAR_N=0 -DGROUP_WAVE_LISTS_N=0``), and a
-library takes a minute to compile: no test builds one.  ``scripts/group_variant_hashes.py`` paints ``variant_cases()``
-below with whatever library is loaded and prints the grids' hashes, for comparing two builds by hand
-(profiles/EXPERIMENTS.md, "Paint grouping"); the suite itself rests on the oracle and on the record and stray counts.
+The earlier grouping (per-lane window decisions, lists shared by the waves) is gone from the tree, and a library takes
+a minute to compile: no test builds a second one.  ``scripts/group_variant_hashes.py`` paints ``variant_cases()`` below
+with whatever library is loaded and prints the grids' hashes, for comparing any two builds by hand - this tree against
+a build of another commit loaded through ``ASTRILD_HIP_LIB``, for example (profiles/EXPERIMENTS.md, "Paint
+grouping"); the suite itself rests on the oracle and on the record and stray counts.
 """
 import hashlib
 
