@@ -145,6 +145,7 @@ SIGNATURES = {
     "ast_smooth_plan_destroy": (_i, [_vp]),
     "ast_gaussian_smooth": (_i, [_vp, _vp, _d, _i, _vp]),
     "ast_minmax": (_i, [_vp, _i, _sz, _vp, _vp]),
+    "ast_absmax_finite": (_i, [_vp, _i, _sz, _vp, _vp]),
     "ast_sum": (_i, [_vp, _i, _sz, _vp, _vp]),
     "ast_flat_power_bin": (_i, [_vp, _vp, _i, _d, _vp, _i, _vp, _vp, _vp]),
     "ast_ring_filter_2d": (_i, [_vp, _vp, _i, _d, _d, _d, _vp]),

@@ -1293,8 +1293,8 @@ column_deposit_kernel(const T* __restrict__ pos, const T* __restrict__ mass, Til
     constexpr int LO = Window<W>::LO, H = W - 1;
     // The LDS tile accumulates in 64-bit FIXED POINT: ds_add_u64 retires ~1.9x the lanes per
     // clock of ds_add_f64 on scattered addresses (scripts/micro/lds_atomics.hip), integer sums
-    // do not depend on arrival order (the whole paint is bit-reproducible), and the quantum
-    // chosen per column below sits far under the rounding of the output type.
+    // do not depend on arrival order (the whole paint is bit-reproducible), and the quantum chosen per column below sits
+    // far under the rounding of the output type - of the HEAVIEST deposit; light cells: DESIGN.md 4.1, "Accuracy of a painted cell".
     //
     // double -> integer is one add with M = 1.5 * 2^52: bits(x + M) = 0x4338 << 48 + round(x).
     //  * T = double: the 0x4338 is stripped per term and sums may use 62 bits.

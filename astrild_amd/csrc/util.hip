@@ -119,7 +119,20 @@ __device__ inline double key2d(unsigned long long k) {
 // The same-address atomics serialise at the memory side: one pair per WAVE (8192 waves) took 0.2 ms for a 134 MB map
 // that streams in 0.03, one pair per 256-thread workgroup (2048 of them) 0.057 ms.
 constexpr int MINMAX_BLOCK = 1024, MINMAX_GRID = 512;
-template <typename T, int V>
+// ABS (ast_absmax_finite): hi collects max |x| and lo a flag instead of the minimum - 0 for a finite element, -1 for NaN or
+// +-Inf (fmax skips a NaN; the flag does not) - so one pass gives the paint its mass bound AND tells it that the bound is usable.
+template <bool ABS>
+__device__ inline void minmax_take(double& lo, double& hi, double v) {
+    if (ABS) {
+        const double a = fabs(v);
+        lo = fmin(lo, a <= DBL_MAX ? 0.0 : -1.0);
+        hi = fmax(hi, a);
+    } else {
+        lo = fmin(lo, v);
+        hi = fmax(hi, v);
+    }
+}
+template <typename T, int V, bool ABS = false>
 __global__ void __launch_bounds__(MINMAX_BLOCK) minmax_kernel(const T* __restrict__ buf, size_t n, unsigned long long* keys) {
     typedef T vec_t __attribute__((ext_vector_type(V)));
     __shared__ double slo[MINMAX_BLOCK / 64], shi[MINMAX_BLOCK / 64];
@@ -135,19 +148,17 @@ __global__ void __launch_bounds__(MINMAX_BLOCK) minmax_kernel(const T* __restric
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
 #pragma unroll
-            for (int k = 0; k < V; ++k) { l[j] = fmin(l[j], (double)v[j][k]); h[j] = fmax(h[j], (double)v[j][k]); }
+            for (int k = 0; k < V; ++k) minmax_take<ABS>(l[j], h[j], (double)v[j][k]);
         }
     }
     double lo = DBL_MAX, hi = -DBL_MAX;
     for (; i < nvec; i += stride) {
         const vec_t v = vb[i];
 #pragma unroll
-        for (int k = 0; k < V; ++k) { lo = fmin(lo, (double)v[k]); hi = fmax(hi, (double)v[k]); }
+        for (int k = 0; k < V; ++k) minmax_take<ABS>(lo, hi, (double)v[k]);
     }
     if (blockIdx.x == 0 && threadIdx.x < n - nvec * V) {           // the elements past the last whole vector
-        const double v = (double)buf[nvec * V + threadIdx.x];
-        lo = fmin(lo, v);
-        hi = fmax(hi, v);
+        minmax_take<ABS>(lo, hi, (double)buf[nvec * V + threadIdx.x]);
     }
     lo = fmin(fmin(lo, l[0]), fmin(fmin(l[1], l[2]), l[3]));
     hi = fmax(fmax(hi, h[0]), fmax(fmax(h[1], h[2]), h[3]));
@@ -529,7 +540,8 @@ extern "C" int ast_accumulate(void* dst, const void* src, int dtype, size_t coun
     return ast_add(dst, src, dst, dtype, count, stream);
 }
 
-extern "C" int ast_minmax(const void* buf, int dtype, size_t count, double* out, void* stream) {
+template <bool ABS>
+static int minmax_launch(const void* buf, int dtype, size_t count, double* out, void* stream) {
     AST_CHECK_ARG(buf && out && count > 0);
     AST_CHECK_ARG(dtype == AST_F32 || dtype == AST_F64);
     hipStream_t s = ast::as_stream(stream);
@@ -540,15 +552,24 @@ extern "C" int ast_minmax(const void* buf, int dtype, size_t count, double* out,
     const size_t need = ((count + per - 1) / per + MINMAX_BLOCK - 1) / MINMAX_BLOCK;
     const unsigned g = (unsigned)(need > (size_t)MINMAX_GRID ? (size_t)MINMAX_GRID : need);
     if (dtype == AST_F32) {
-        if (wide) minmax_kernel<float, 4><<<g, MINMAX_BLOCK, 0, s>>>((const float*)buf, count, keys);
-        else minmax_kernel<float, 1><<<g, MINMAX_BLOCK, 0, s>>>((const float*)buf, count, keys);
+        if (wide) minmax_kernel<float, 4, ABS><<<g, MINMAX_BLOCK, 0, s>>>((const float*)buf, count, keys);
+        else minmax_kernel<float, 1, ABS><<<g, MINMAX_BLOCK, 0, s>>>((const float*)buf, count, keys);
     } else {
-        if (wide) minmax_kernel<double, 2><<<g, MINMAX_BLOCK, 0, s>>>((const double*)buf, count, keys);
-        else minmax_kernel<double, 1><<<g, MINMAX_BLOCK, 0, s>>>((const double*)buf, count, keys);
+        if (wide) minmax_kernel<double, 2, ABS><<<g, MINMAX_BLOCK, 0, s>>>((const double*)buf, count, keys);
+        else minmax_kernel<double, 1, ABS><<<g, MINMAX_BLOCK, 0, s>>>((const double*)buf, count, keys);
     }
     minmax_finish<<<1, 1, 0, s>>>(keys);
     AST_CHECK_LAUNCH();
     return AST_OK;
+}
+
+extern "C" int ast_minmax(const void* buf, int dtype, size_t count, double* out, void* stream) {
+    return minmax_launch<false>(buf, dtype, count, out, stream);
+}
+
+// out[0] = 0 when every element is finite, -1 when one is NaN or +-Inf; out[1] = max |x| (NaN skipped, Inf kept)
+extern "C" int ast_absmax_finite(const void* buf, int dtype, size_t count, double* out, void* stream) {
+    return minmax_launch<true>(buf, dtype, count, out, stream);
 }
 
 extern "C" int ast_sum(const void* buf, int dtype, size_t count, double* out, void* stream) {

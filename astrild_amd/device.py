@@ -395,6 +395,21 @@ def _max_abs(t, count):
     return float(lo_hi.abs().max()) or 1.0
 
 
+def _mass_bound(mass, count):
+    """The tiled overwrite paint's mass bound, max |mass| (1.0 for None, nothing or all zeros), what its fixed-point quantum is
+    scaled by - and the place where a NaN or Inf mass is refused, before any paint kernel runs: the column walk adds the bit
+    pattern of ``fma(NaN, ...)`` as an integer (finite garbage in the cells the particle touches), and one Inf mass makes the
+    quantum infinite (the whole grid NaN).  One reduction for both (ast_absmax_finite), one 16-byte fetch."""
+    if mass is None or not count:
+        return 1.0
+    flag_max = torch.empty(2, dtype=torch.float64, device=mass.device)
+    check(_lib.lib().ast_absmax_finite(ptr(mass), real_code(mass), count, ptr(flag_max), stream()), "ast_absmax_finite")
+    flag, bound = flag_max.tolist()
+    if flag != 0.0:
+        raise ValueError("paint: a mass is NaN or Inf (the tiled paint accumulates in fixed point, scaled by max |mass|)")
+    return bound or 1.0
+
+
 def _offset_planes(offset_planes):          # (first buffer plane, count) that get the offset; default: all
     return (0, -1) if offset_planes is None else (int(offset_planes[0]), int(offset_planes[1]))
 
@@ -450,6 +465,22 @@ def paint(pos, mass, nmesh, boxsize, window="cic", scale=1.0, out=None, method="
       no hint, >= 2^20 particles, not whole, check_dropped         sample_is_unordered -> scattered, else single-pass
       otherwise                                                    single-pass
     Repaints after an attempt (overflow list too long, late list full): :func:`next_paint_path`.
+
+    Accuracy (derived in tests/paint_accuracy.py, measured in DESIGN.md 4.1 "Accuracy of a painted cell").  A tiled overwrite
+    paint whose overflow / late list stays empty stores in every cell the sum S of its K deposits with
+      |cell - (S - offset)| <= K q / 2 + u |S - offset| + (c_h u + c_d 2^-53) (A + |offset|),
+    A = sum of |deposits|, u = 2^-24 (float32) or 2^-53 (float64), c_h = 0, 1 or 3 (cells on the border of the 8 x 8 tile
+    footprint), c_d = 18 (CIC) or 36 (TSC), and the quantum q = max |mass| * |scale| / 2^k, k = min(50, B - bits), B = 47
+    (float32) or 62 (float64), 2^bits > 2 cmax >= 2^(bits - 1), cmax = 5 tile capacities ("tiled": k = 31 / 46 at 1024^3 with
+    one particle per cell) or the fullest tile of the cell's tile column ("tiled2").  So a cell whose mean deposit is rho
+    times lighter than the heaviest particle's is good to rho / 2^(k + 1) of itself - rho 2^-32 / rho 2^-47 at 1024^3 - and
+    deposits below q / 2 vanish; only for rho <= 2^(k - 23) (float32) is that under the rounding of the grid dtype.  The grid
+    is bit-reproducible and scales exactly with powers of two in mass, scale and (positions, boxsize).  Deposits made with
+    float atomics ("direct", accumulate, the overflow and late lists) form weights and products in the grid dtype: add
+    (2 K + 13) u (A + |prefill|) + 3 u D, D = sum over the deposits of |m scale| (wy wz + wx wz + wx wy): a particle leaves an
+    error of up to 3 u of its own mass in a cell it touches with a tiny weight.
+    A NaN or Inf mass raises ValueError before a tiled overwrite paint launches anything (found by the reduction that computes
+    max |mass|); "direct" and accumulating paints have no such reduction and carry it into the cells the particle touches.
     """
     L = _lib.lib()
     n = int(nmesh)
@@ -495,12 +526,13 @@ def paint(pos, mass, nmesh, boxsize, window="cic", scale=1.0, out=None, method="
         offset = total_mass(mass, npart) * float(scale) / float(n) ** 3
     dropped, nd = torch.zeros(1, dtype=torch.int64, device=pos.device), None
     if use_tiled:
+        mass_bound = 1.0 if accumulate else _mass_bound(mass, npart)      # (raises on a NaN / Inf mass: before the probes)
         choice = (method, accumulate, hint, whole, check_dropped, npart)
         kind = paint_probe_kind(*choice)
         probed = probe_input(pos, n, boxsize, shift) if kind == "input" else None
         unordered = sample_is_unordered(pos, n, boxsize, shift) if kind == "order" else None
         path = first_paint_path(*choice, probed, unordered, scatter_overflow_limit(pos.dtype, npart) if probed else None)
-        mass_bound, attempts = 1.0 if accumulate else _max_abs(mass, npart), 0
+        attempts = 0
         while True:
             attempts += 1
             flags = paint_flags(path, accumulate, defer_fold, hint == "xsorted")
@@ -573,7 +605,7 @@ class StagedPaint:
             raise _lib.AstrildHipError("staged paint needs a CIC/TSC window and nmesh a multiple of 32")
         self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=pos.device)
         self.dropped = torch.zeros(1, dtype=torch.int64, device=pos.device)
-        self.mass_bound = _max_abs(mass, self.npart)
+        self.mass_bound = _mass_bound(mass, self.npart)
         self.args = (float(boxsize), float(scale), int(x_start), self.nx)
         self.tail = (self.mass_bound, float(offset), *_offset_planes(offset_planes), float(shift))
         self.row_planes = int(L.ast_paint_tile_row_planes())

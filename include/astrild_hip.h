@@ -751,6 +751,10 @@ int ast_sum(const void* buf_d, int dtype, size_t count, double* out_d, void* str
 /* min and max of a buffer -> out_d[0], out_d[1] (double, device). */
 int ast_minmax(const void* buf_d, int dtype, size_t count, double* out_d, void* stream);
 
+/* The paint's mass bound, in the same single pass: out_d[1] = max |x| and out_d[0] = 0.0 when every element is
+ * finite, -1.0 when at least one is NaN or +-Inf (then out_d[1] skips the NaNs and is Inf if an Inf is among them). */
+int ast_absmax_finite(const void* buf_d, int dtype, size_t count, double* out_d, void* stream);
+
 /* np.histogram(data, bins=nbins, range=(lo, hi)) counts: uniform bins,
  * right-most bin closed (SkyArray.pdf, rays/skys/sky_array.py:428-433).
  * counts_d (int64, nbins) is ACCUMULATED into. */

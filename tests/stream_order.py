@@ -328,7 +328,7 @@ for _dtype in (np.float32, np.float64):
             case(name=f"paint_{_method}_{_id}", covers=("paint",), make=_two(_particles(_dtype)), check=_check_particles,
                  call=lambda dev, lens, p, m, w=_window, me=_method: dev.paint(p, m, N_MESH, L_BOX, w, method=me,
                                                                                 accumulate=False),
-                 host_syncs=True, sync_line="_max_abs: float(lo_hi.abs().max()); paint: st.cpu().tolist(), dropped.item()",
+                 host_syncs=True, sync_line="_mass_bound: flag_max.tolist(); paint: st.cpu().tolist(), dropped.item()",
                  **_PAINT_REFUSES)
 case(name="paint_tiled_unchecked", covers=("paint",), make=_two(_particles(np.float32, masses=False)),
      check=_check_particles,
@@ -371,7 +371,7 @@ def _staged_paint(dev, lens, pos, mass):
 
 case(name="staged_paint", covers=("StagedPaint.group", "StagedPaint.walk", "StagedPaint.fold"),
      make=_two(_particles(np.float32)), check=_check_particles, call=_staged_paint,
-     host_syncs=True, sync_line="StagedPaint.__init__: _max_abs(mass); check(): int(self.dropped.item())", **_PAINT_REFUSES)
+     host_syncs=True, sync_line="StagedPaint.__init__: _mass_bound(mass); check(): int(self.dropped.item())", **_PAINT_REFUSES)
 
 
 def _xsorted_particles(seed):

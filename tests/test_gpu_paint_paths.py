@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from oracle import mesh as omesh, fftpower as offt
+from tests import paint_accuracy as pa
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -116,6 +117,15 @@ class _Input:
                                            N, L, window)
         return self._grids[key]
 
+    def accuracy(self, window, masses):
+        """The per-cell quantities of tests/paint_accuracy.py around the oracle grid (K and the quanta: once per window)."""
+        key = ("acc", window, masses)
+        if key not in self._grids:
+            mass = self.mass.astype(np.float64) if masses else None
+            self._grids[key] = pa.OracleReference(self.pos.astype(np.float64), mass, N, L, window, self.oracle(window, masses),
+                                                  share=self._grids.get(("acc", window, not masses)))
+        return self._grids[key]
+
 
 @pytest.fixture(scope="module")
 def dev(hip):
@@ -136,8 +146,16 @@ def inputs(dev):
     return get
 
 
-def _check_grid(grid, ref, total, dtype):
+def _check_grid(grid, ref, total, dtype, acc=None, path=None):
     got = grid.cpu().numpy().astype(np.float64)
+    if acc is not None:
+        # cell by cell, the any-path bound of tests/paint_accuracy.py (path unknown: the looser of the two list formats per cell)
+        T = np.float32 if dtype == "f32" else np.float64
+        lists = ["two-pass"] if path == TP else ["single"] if path in (SP, SC) else ["single", "two-pass"]
+        bound = np.maximum.reduce([acc.any_bound(T, l) for l in lists])
+        ratio, rel, over = pa.measure(got, acc, bound)
+        print(f"    per cell: error / bound {ratio:.3g}, error / A {rel:.3g}")
+        assert over == 0, (ratio, rel, over)
     if dtype == "f64":
         np.testing.assert_allclose(got, ref, rtol=1e-11, atol=1e-11 * ref.max())
         assert got.sum() == pytest.approx(total, rel=1e-12)
@@ -155,13 +173,13 @@ def _paint_and_check(dev, inp, dtype, window, masses, want_path, want_attempts=1
     assert (st["path"], st["attempts"]) == (want_path, want_attempts), st
     if st["path"] == SC:
         assert st["overflow"] <= _late_capacity(dev, dtype), st            # the late list held every record
-    ref = inp.oracle(window, masses)
-    _check_grid(grid, ref, inp.total(masses), dtype)
+    ref, acc = inp.oracle(window, masses), inp.accuracy(window, masses)
+    _check_grid(grid, ref, inp.total(masses), dtype, acc, st["path"])
     # nothing on a whole periodic grid raises, and not checking the drop count loses nothing
     again = dev.paint(pos, mass, N, L, window, method="tiled", accumulate=False, check_dropped=False, **kw)
     if st["path"] == SC and st["overflow"] > 0:
         # (the late list is added with float atomics: the order, hence the last bits, varies from call to call)
-        _check_grid(again, ref, inp.total(masses), dtype)
+        _check_grid(again, ref, inp.total(masses), dtype, acc, st["path"])
     else:
         assert torch.equal(grid, again)
     return st
@@ -203,7 +221,7 @@ def test_scattered_hint_never_loses_a_deposit(dev, inputs, dtype, window):
     pos, mass = inp.device(dtype, True)
     grid = dev.paint(pos, mass, N, L, window, method="tiled", accumulate=False, hint="scattered", check_dropped=False)
     ref = inp.oracle(window, True)
-    _check_grid(grid, ref, inp.total(True), dtype)
+    _check_grid(grid, ref, inp.total(True), dtype, inp.accuracy(window, True), SC if dtype == "f32" else TP)
     st = {}
     dev.paint(pos, mass, N, L, window, method="tiled", accumulate=False, hint="scattered", check_dropped=False, stats=st)
     assert (st["path"], st["attempts"]) == ((SC, 1) if dtype == "f32" else (TP, 2)), st
