@@ -26,6 +26,7 @@ PVPDF_MAX_BINS = 1 << 22                    # ast_pairwise_pdf_max_bins(), known
 PVPDF_MAX_MOMENT_ROWS = 480                 # without a library call (AST_PVPDF_MAX_MOMENT_ROWS)
 PAIRVEL_KIND = {"radial": 0, "los": 1}      # AST_PAIRVEL_*
 PAIRVEL_MAX_BINS = 511                      # ast_pairvel_max_bins() (AST_PAIRVEL_MAX_BINS), known here likewise
+PLANE_GEOMETRY = {"box": 0, "cone": 1}      # AST_PLANE_*
 TPCF_JK_MAX_TABLE = 1 << 22                 # ast_tpcf_jk_max_table(): regions x bins of a jackknife, likewise
 
 
@@ -227,6 +228,10 @@ SIGNATURES = {
     "ast_fof_relabel": (_i, [_vp, _vp, _sz, _vp, _vp]),
     "ast_fof_features": (_i, [_vp, _i, _vp, _i, _vp, _i, _sz, _vp, _vp, _vp, _sz, _d, _vp, _vp, _vp, _vp]),
     "ast_readout": (_i, [_i, _i, _i, _vp, _i, _i, _vp, _sz, _d, _d, _vp, _vp]),
+    "ast_plane_paint_exponent": (_i, [_sz]),
+    "ast_plane_paint_accumulate": (_i, [_i, _i, _i, _vp, _vp, _sz, _sz, _i, _i, _i, _d, _d, _d, ct.POINTER(_d), _vp, _d, _d,
+                                        _vp, _vp, _vp]),
+    "ast_plane_paint_finish": (_i, [_i, _i, _vp, _vp, _vp, _i, _i, _d, _vp, _vp]),
 }
 
 _lib = None

@@ -1306,6 +1306,44 @@ int ast_fof_features(const void* pos_d, int pos_dtype, const void* vel_d, int ve
 int ast_readout(int window, int field_dtype, int pos_dtype, const void* field_d, int nmesh, int ncomp, const void* pos_d,
                 size_t np, double boxsize, double shift_cells, void* out_d, void* stream);
 
+/* ------------------------------------------------------------- lens planes: particles -> P planes of npix x npix
+ * Projected mass assignment for a periodic box (plane-parallel) and a light cone (gnomonic map, radial shells), with
+ * the NGP / CIC / TSC window on the two transverse axes.  No reference counterpart: the reference reads its planes
+ * from Ray-Ramses output (hard part 6).  DESIGN.md 6n holds the contract in full; in short:
+ *
+ * ast_plane_paint_accumulate: sums_d (nplanes, npix, npix) int64 += the deposits of np particles.  pos_d (np, 3) and
+ * mass_d (np; NULL: 1) of `dtype`.  All arithmetic in double, one rounding per written operation:
+ *   ms = (double)mass * scale; a particle with !(|ms| <= vmax) is REFUSED (counters_d[2]) and deposits nothing.
+ *   (a, b): the two axes other than `los`, in increasing order; sums is indexed [plane][ia][ib].
+ *   AST_PLANE_BOX:  sl = x_los * cl, plane = floor(sl) mod nplanes; s_a = x_a * c1 + c0 (two roundings); base pixel,
+ *       offset and the periodic stencil as in ast_paint.  A particle whose sl, s_a or s_b is not finite is outside
+ *       (counters_d[0]).  Every finite coordinate is reduced modulo the period and deposited.
+ *   AST_PLANE_CONE: d = x - origin (host, 3 doubles); outside (counters_d[0]) when a d is not finite, d_los <= 0, or
+ *       r2 = (d0 d0 + d1 d1) + d2 d2 is not in [e2_d[0], e2_d[nplanes]); plane p has e2_d[p] <= r2 < e2_d[p + 1]
+ *       (e2_d: nplanes + 1 ascending doubles on the device).  s_a = (d_a / d_los) * c1 + c0; base = floor(s) (CIC) or
+ *       floor(s + 1/2), offset s - base, base clamped in double to [-2, npix + 1]; stencil points outside [0, npix)
+ *       are dropped: all of them - outside; some - clipped (counters_d[1]).
+ *   Weights as Window<W>::weights<double>, not renormalised.  Term (ms wa[i]) wb[j], times invq = 2^k / vmax, rounded
+ *   to the nearest integer (ties to even) and added with a 64-bit integer atomic; k = ast_plane_paint_exponent(np_total),
+ *   np_total >= np the declared bound on all particles ever added to these sums: they cannot overflow, and they hold
+ *   the same bits for every particle order, chunking and launch geometry.
+ * counters_d: 3 uint64 on the device, added to.  np == 0: AST_OK without a launch.
+ *
+ * ast_plane_paint_exponent: host only; min(50, 62 - bit_length(np_total)), -1 for np_total >= 2^60.
+ *
+ * ast_plane_paint_finish: out[p][ia][ib] = (out_dtype)(v + add_d[p]), v = (double)sums * mul_d[p], in the cone
+ * v = v * (w * sqrt(w)), w = (1 + ta ta) + tb tb, ta = ((ia + 0.5) - npix / 2) / c1: the cos^-3 that gives gnomonic
+ * pixels equal solid angle.  mul_d, add_d: nplanes doubles on the device.  Every element of out_d is written. */
+#define AST_PLANE_BOX 0
+#define AST_PLANE_CONE 1
+int ast_plane_paint_exponent(size_t np_total);
+int ast_plane_paint_accumulate(int geometry, int window, int dtype, const void* pos_d, const void* mass_d, size_t np,
+                               size_t np_total, int los, int nplanes, int npix, double cl, double c1, double c0,
+                               const double* origin, const double* e2_d, double scale, double vmax, long long* sums_d,
+                               unsigned long long* counters_d, void* stream);
+int ast_plane_paint_finish(int geometry, int out_dtype, const long long* sums_d, const double* mul_d, const double* add_d,
+                           int nplanes, int npix, double c1, void* out_d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
