@@ -16,6 +16,8 @@
 // are C * 8 B = 128 B contiguous per row of the tile; every thread keeps R1 (R2)
 // independent 8-byte loads in flight.
 #include "ast_common.h"
+#include "fft_roots.h"
+#include "lowk_sums.h"
 #include "paint_tile_geom.h"
 #include <algorithm>
 #include <cmath>
@@ -41,21 +43,18 @@ __device__ constexpr float kSin32[16] = {
 // pair and a multiply two packed instructions (v_pk_mul_f32 + v_pk_fma_f32 with lane selects).  Written
 // component-wise on float2 the compiler also packs, but across DIFFERENT numbers, and pays for it with
 // one v_mov_b32 per operand (439 moves next to 592 packed instructions in the 1024-point pass).
-#ifndef FFT_NT
-#define FFT_NT 3                    // 1 nontemporal loads, 2 nontemporal stores, 3 both
-#endif
-// Nontemporal accesses for arrays that are streamed through once per pass and are far larger than the caches: the three
+// Nontemporal accesses (NT: loads and stores both) for arrays that are streamed through once per pass and are far larger than the caches: the three
 // forward passes at N = 1024 (4.4 GB: z 2.15 -> 2.11, y 2.06 -> 2.00, x 1.28 -> 1.19 ms).  NOT for smaller cubes or the
 // inverse passes of the bispectrum, which read one 0.5 GB spectrum 31 times out of the Infinity Cache (19.6 -> 22.3 ms with them).
 typedef float f2v __attribute__((ext_vector_type(2)));
 template <bool NT>
 __device__ inline float2 ld_stream(const float2* p) {
-    if (NT && (FFT_NT & 1)) { const f2v v = __builtin_nontemporal_load(reinterpret_cast<const f2v*>(p)); return make_float2(v.x, v.y); }
+    if (NT) { const f2v v = __builtin_nontemporal_load(reinterpret_cast<const f2v*>(p)); return make_float2(v.x, v.y); }
     return *p;
 }
 template <bool NT>
 __device__ inline void st_stream(float2* p, float2 v) {
-    if (NT && (FFT_NT & 2)) __builtin_nontemporal_store(f2v{v.x, v.y}, reinterpret_cast<f2v*>(p));
+    if (NT) __builtin_nontemporal_store(f2v{v.x, v.y}, reinterpret_cast<f2v*>(p));
     else *p = v;
 }
 typedef float cf2 __attribute__((ext_vector_type(2)));
@@ -67,15 +66,8 @@ __device__ inline cf2 cmul_cf(cf2 a, cf2 w) {
 }
 __device__ inline float2 cmul(float2 a, float2 w) { return from_cf(cmul_cf(to_cf(a), to_cf(w))); }
 
-constexpr int bitrev(int v, int bits) {
-    int r = 0;
-    for (int i = 0; i < bits; ++i) r |= ((v >> i) & 1) << (bits - 1 - i);
-    return r;
-}
-constexpr int ilog2(int v) { return v <= 1 ? 0 : 1 + ilog2(v / 2); }
-
 // In-register forward FFT of R points, decimation in frequency.  On return X[k]
-// sits in v[bitrev(k)].  Fully unrolled: every index and twiddle is a constant.
+// sits in v[bitrev(k)] (bitrev, ilog2: fft_roots.h).  Fully unrolled: every index and twiddle is a constant.
 template <int R>
 __device__ inline void fft_reg(float2 (&vv)[R]) {
     cf2 v[R];
@@ -144,9 +136,6 @@ struct ShellMask { const float2* src; long long lo2, hi2; int ky0 = 0; int pass 
 // work array and radii.  Thirty-one shells used to be 93 launches of 0.06-0.4 ms each, most of them far too small to fill
 // the chip to the end; batched, the shells of a launch fill each other's tails.
 constexpr int SHELL_BATCH = 8;
-#ifndef C2C_XCD_MODE
-#define C2C_XCD_MODE 2              // batch rows -> XCDs in strided_c2c_kernel: 0 never, 1 inverse passes, 2 all passes
-#endif
 #ifndef XPASS_ATOMICS
 #define XPASS_ATOMICS 1             // perf experiments on the binning epilogue's ds_add_f64 (scripts/perf_xpass_variants.py): 0 = none, 2 = lane-unique addresses
 #endif
@@ -187,19 +176,17 @@ strided_c2c_kernel(float2* __restrict__ data, const float2* __restrict__ tw_g, s
     float2* tw = lds + YN * C;       // exp(-2 pi i m / N)
     double* shell = reinterpret_cast<double*>(lds + YN * C + N);    // [NB + 1] when POWER
     unsigned tile = blockIdx.x % tiles_per_batch, b = blockIdx.x / tiles_per_batch;
-#if C2C_XCD_MODE
     // A 16-column tile row is 128 bytes at an 8-byte-aligned address (row pitch N / 2 + 1): every line it touches is shared
     // with the neighbouring column tile.  Consecutive workgroups go to consecutive XCDs (observed round-robin placement;
     // a matter of speed only), so neighbouring tiles sat behind different L2s and each fetched the shared lines - the
-    // masked inverse passes read 1.94 x their bytes (scripts/pmc_per_launch.py).  Here the tiles of one batch row follow each
-    // other on ONE XCD: batch b runs on XCD b mod 8.  512^3 bispectrum: x / y inverse passes 6.9 -> 5.9 ms; forward passes
-    // 512^3 0.52 -> 0.46 ms, 256^3 0.069 -> 0.050 ms, 1024^3 (32-column tiles) -0.05 ms per step.
-    if ((INV || C2C_XCD_MODE == 2) && (gridDim.x / tiles_per_batch) % 8u == 0u) {
+    // masked inverse passes read 1.94 x their bytes (scripts/pmc_per_launch.py).  Here, in every pass, the tiles of one batch
+    // row follow each other on ONE XCD: batch b runs on XCD b mod 8.  512^3 bispectrum: x / y inverse passes 6.9 -> 5.9 ms;
+    // forward passes 512^3 0.52 -> 0.46 ms, 256^3 0.069 -> 0.050 ms, 1024^3 (32-column tiles) -0.05 ms per step.
+    if ((gridDim.x / tiles_per_batch) % 8u == 0u) {
         const unsigned xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3;
         b = (slot / tiles_per_batch) * 8u + xcd;
         tile = slot % tiles_per_batch;
     }
-#endif
     const size_t c0 = (size_t)tile * C;
     if (INV && sb.count > 0) {                        // this workgroup's shell of the batch (uniform)
         data = sb.work[blockIdx.y];
@@ -888,28 +875,17 @@ rows_c2r_kernel(const float2* __restrict__ in, float* __restrict__ out, const fl
     __syncthreads();
     // z[j] = conj(result[j]); x[2j] = 2 Re z, x[2j+1] = 2 Im z
     const float s2 = 2.0f * scale;
-#ifndef C2R_ST
-#define C2R_ST 2                  // 0 = 8-byte stores, 1 = 16-byte stores, 2 = 16-byte NONTEMPORAL stores.  Measured on the 512^3 bispectrum
-                                  // (31 shells): this pass 6.5 / 6.0 / 6.1 ms, and with 2 the NEXT shell's masked x / y passes 7.5 -> 6.8 ms:
-                                  // the 0.5 GB real cube no longer pushes the 0.5 GB spectrum they re-read out of the Infinity Cache
-#endif
-    if (C2R_ST) {
-        typedef float f4v __attribute__((ext_vector_type(4)));
-        for (int i = threadIdx.x; i < C * (M / 2); i += NT) {
-            const int rr = i / (M / 2), j = (i % (M / 2)) * 2;
-            if (row0 + rr >= nrows) continue;
-            const float2 z0 = Y[rr * MP + j], z1 = Y[rr * MP + j + 1];
-            const f4v o = {z0.x * s2, -z0.y * s2, z1.x * s2, -z1.y * s2};
-            f4v* dst = reinterpret_cast<f4v*>(out + (row0 + rr) * out_pitch) + j / 2;
-            if (C2R_ST == 2) __builtin_nontemporal_store(o, dst); else *dst = o;
-        }
-        return;
-    }
-    for (int i = threadIdx.x; i < C * M; i += NT) {
-        const int rr = i / M, j = i % M;
+    // 16-byte NONTEMPORAL stores.  Measured on the 512^3 bispectrum (31 shells): this pass 6.1 ms (6.5 with 8-byte stores), and
+    // the NEXT shell's masked x / y passes 7.5 -> 6.8 ms: the 0.5 GB real cube no longer pushes the 0.5 GB spectrum they
+    // re-read out of the Infinity Cache
+    typedef float f4v __attribute__((ext_vector_type(4)));
+    for (int i = threadIdx.x; i < C * (M / 2); i += NT) {
+        const int rr = i / (M / 2), j = (i % (M / 2)) * 2;
         if (row0 + rr >= nrows) continue;
-        const float2 z = Y[rr * MP + j];
-        reinterpret_cast<float2*>(out + (row0 + rr) * out_pitch)[j] = make_float2(z.x * s2, -z.y * s2);
+        const float2 z0 = Y[rr * MP + j], z1 = Y[rr * MP + j + 1];
+        const f4v o = {z0.x * s2, -z0.y * s2, z1.x * s2, -z1.y * s2};
+        f4v* dst = reinterpret_cast<f4v*>(out + (row0 + rr) * out_pitch) + j / 2;
+        __builtin_nontemporal_store(o, dst);
     }
 }
 
@@ -926,9 +902,7 @@ struct TriShells { const float2* work[TRI_ROWS]; int kmax[TRI_ROWS]; int count; 
 
 template <int R1, int R2>
 __global__ void __launch_bounds__(TRI_ROWS * R2)
-#ifndef TRI_OCC_FREE
 __attribute__((amdgpu_waves_per_eu(4, 4)))          // 128 VGPRs: two 512-thread workgroups per CU (74 KB of LDS each) up to n = 512
-#endif
 rows_c2r_triangles_kernel(TriShells sh, const float2* __restrict__ tw_g, size_t nrows, size_t in_pitch, const int* __restrict__ tri,
                           int ntri, int parts, double* __restrict__ partial) {
     constexpr int C = TRI_ROWS, M = R1 * R2, N = 2 * M, NT = C * R2, R2P = R2 + 1, MP = M + 1;
@@ -1031,10 +1005,7 @@ rows_c2r_triangles_kernel(TriShells sh, const float2* __restrict__ tw_g, size_t 
         // the next position's rows: in flight across the product loop (the longest phase, and the one with the fewest live
         // registers - held across the two register FFTs the 34 extra VGPRs spilled)
         if (PREFETCH && pos + gridDim.x < nrows) fetch(pos + gridDim.x);
-#ifndef TRI_FUSE_ABLATE
-#define TRI_FUSE_ABLATE 0           // perf experiments: 1 = no products, 2 = no global loads, 4 = no transform
-#endif
-        if (worker && !(TRI_FUSE_ABLATE & 1)) {
+        if (worker) {
             // two cells per LDS read; the part's <= N / parts products are summed in fp32 (each product carries 6e-8 already;
             // ~90 terms add 6e-7 of the PART's sum, random from part to part), the parts and positions in double
             const float* f = reinterpret_cast<const float*>(Y);
@@ -1091,24 +1062,7 @@ triangles_reduce_kernel(const double* __restrict__ partial, int nblocks, int nth
 // Deterministic (fixed summation trees).  The grid may hold rho or rho - mean: only the unused DC mode differs.
 constexpr int MLOW = 5;                  // shells 0..4 (|m| in [1, 6), by the binning rule) are taken from the double-precision sums
 constexpr int MBOX = MLOW + 1;           // modes |m_i| <= MBOX are evaluated: under the float64 rule a vector of norm exactly 6 may fall into shell 4
-// e^{-2 pi i r / 32} for odd r: (kC32o[r / 2], kS32o[r / 2]) - cos and -sin of pi r / 16
-__device__ constexpr double kC32o[16] = {0.98078528040323044, 0.83146961230254524, 0.55557023301960222, 0.19509032201612827,
-                                         -0.19509032201612827, -0.55557023301960222, -0.83146961230254524, -0.98078528040323044,
-                                         -0.98078528040323044, -0.83146961230254524, -0.55557023301960222, -0.19509032201612827,
-                                         0.19509032201612827, 0.55557023301960222, 0.83146961230254524, 0.98078528040323044};
-__device__ constexpr double kS32o[16] = {-0.19509032201612827, -0.55557023301960222, -0.83146961230254524, -0.98078528040323044,
-                                         -0.98078528040323044, -0.83146961230254524, -0.55557023301960222, -0.19509032201612827,
-                                         0.19509032201612827, 0.55557023301960222, 0.83146961230254524, 0.98078528040323044,
-                                         0.98078528040323044, 0.83146961230254524, 0.55557023301960222, 0.19509032201612827};
-// e^{-2 pi i r / 16} = (kC16[r], kS16[r])
-__device__ constexpr double kC16[16] = {1.0, 0.92387953251128674, 0.70710678118654752, 0.38268343236508977, 0.0,
-                                        -0.38268343236508977, -0.70710678118654752, -0.92387953251128674, -1.0,
-                                        -0.92387953251128674, -0.70710678118654752, -0.38268343236508977, 0.0,
-                                        0.38268343236508977, 0.70710678118654752, 0.92387953251128674};
-__device__ constexpr double kS16[16] = {0.0, -0.38268343236508977, -0.70710678118654752, -0.92387953251128674, -1.0,
-                                        -0.92387953251128674, -0.70710678118654752, -0.38268343236508977, 0.0,
-                                        0.38268343236508977, 0.70710678118654752, 0.92387953251128674, 1.0,
-                                        0.92387953251128674, 0.70710678118654752, 0.38268343236508977};
+// (the 16th and odd 32nd roots of unity of the z sums: kC16 / kS16 / kC32o / kS32o, fft_roots.h)
 
 // One level of a TRANSPOSED wave reduction: the lanes whose `mask` bit is clear keep the lower half of the `count`
 // running sums, the others the upper half, and each adds its partner's half - half the work of a plain xor tree at
@@ -1143,8 +1097,8 @@ lowk_z_kernel(const float* __restrict__ grid, const float* __restrict__ rec, int
             float fr[NJ];
 #pragma unroll
             for (int j = 0; j < NJ; ++j) fr[j] = in[lane + 64 * j];
-            if (FOLDW != 0) {
-                constexpr int W = FOLDW != 0 ? FOLDW : 2;
+            if (FOLDW != 0) {                            // (written out here and in cube_fft.hip's biglow_z_kernel: as a shared
+                constexpr int W = FOLDW != 0 ? FOLDW : 2;        // function it compiles to other code in both)
                 const float* src[3];
                 const int ns = ast::halo_sources<float, W>(rec, (int)(row / n), (int)(row % n), n, n / ast::TX, n / ast::TY, src);
                 if (ns > 0) {                            // the records first, then onto the row: the fold's order,
@@ -1210,93 +1164,8 @@ lowk_z_kernel(const float* __restrict__ grid, const float* __restrict__ rec, int
     }
 }
 
-// One axis of the low-k transform: in[(outer * nt + t) * inner + i], t < nt, is summed with e^{-2 pi i k (t0 + t) / n} for
-// k = -MBOX..MBOX.  Block (outer, part) adds up the t of part `part` (of gridDim.y), four independent accumulators so
-// that several loads are in flight, and writes out[((outer * nparts + part) * (2 MBOX + 1) + k + MBOX) * inner + i].
-// y pass: outer = x plane, inner = MBOX + 1, one part.  x pass: outer = 1, inner = (2 MBOX + 1)(MBOX + 1), LOWK_XPARTS
-// parts, then lowk_parts_reduce_kernel adds the parts in order.
+// The y and x sums of the box (lowk_axis_kernel<MBOX>, lowk_sums.h; the x sums in LOWK_XPARTS parts, added in order).
 constexpr int LOWK_XPARTS = 64;
-__global__ void __launch_bounds__(256)
-lowk_axis_kernel(const double2* __restrict__ in, int n, int nt, int t0, int inner, double2* __restrict__ out) {
-    extern __shared__ double2 tw[];                       // e^{-2 pi i t / n}
-    for (int t = threadIdx.x; t < n; t += 256) {
-        double sn, cs;
-        sincospi(-2.0 * (double)t / (double)n, &sn, &cs);
-        tw[t] = make_double2(cs, sn);
-    }
-    __syncthreads();
-    const size_t outer = blockIdx.x;
-    const int nparts = gridDim.y, part = blockIdx.y;
-    const int per = (nt + nparts - 1) / nparts, ta = part * per, tb = min(nt, ta + per);
-    const int nout = (2 * MBOX + 1) * inner;
-    if (nout <= 128) {
-        // few outputs (the y pass: 91): 256 / nout thread groups share the t range, interleaved, and their partial
-        // sums are added in group order
-        __shared__ double2 part_sum[256];
-        const int groups = 256 / nout, o = threadIdx.x % nout, gq = threadIdx.x / nout;
-        double re = 0.0, im = 0.0, re2 = 0.0, im2 = 0.0;
-        if (gq < groups) {
-            const int k = o / inner - MBOX, i = o % inner;
-            int t = ta + gq;
-            for (; t + groups < tb; t += 2 * groups) {           // two loads in flight
-                const double2 v = in[(outer * nt + t) * inner + i], v2 = in[(outer * nt + t + groups) * inner + i];
-                const double2 w = tw[(unsigned)(k * (t0 + t)) & (unsigned)(n - 1)];
-                const double2 w2 = tw[(unsigned)(k * (t0 + t + groups)) & (unsigned)(n - 1)];
-                re += v.x * w.x - v.y * w.y;
-                im += v.x * w.y + v.y * w.x;
-                re2 += v2.x * w2.x - v2.y * w2.y;
-                im2 += v2.x * w2.y + v2.y * w2.x;
-            }
-            if (t < tb) {
-                const double2 v = in[(outer * nt + t) * inner + i];
-                const double2 w = tw[(unsigned)(k * (t0 + t)) & (unsigned)(n - 1)];
-                re += v.x * w.x - v.y * w.y;
-                im += v.x * w.y + v.y * w.x;
-            }
-        }
-        part_sum[threadIdx.x] = make_double2(re + re2, im + im2);
-        __syncthreads();
-        if (gq == 0) {
-            double sr = 0.0, si = 0.0;
-            for (int q = 0; q < groups; ++q) { sr += part_sum[q * nout + o].x; si += part_sum[q * nout + o].y; }
-            const int k = o / inner - MBOX, i = o % inner;
-            out[((outer * nparts + part) * (2 * MBOX + 1) + k + MBOX) * inner + i] = make_double2(sr, si);
-        }
-        return;
-    }
-    for (int o = threadIdx.x; o < nout; o += 256) {
-        const int k = o / inner - MBOX, i = o % inner;
-        double re[4] = {0.0, 0.0, 0.0, 0.0}, im[4] = {0.0, 0.0, 0.0, 0.0};
-        for (int tq = ta; tq < tb; tq += 4) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int t = min(tq + q, tb - 1);        // unconditional load; the duplicate is not added
-                const double2 v = in[(outer * nt + t) * inner + i];
-                const double2 w = tw[(unsigned)(k * (t0 + t)) & (unsigned)(n - 1)];       // n is a power of two
-                if (tq + q < tb) {
-                    re[q] += v.x * w.x - v.y * w.y;
-                    im[q] += v.x * w.y + v.y * w.x;
-                }
-            }
-        }
-        out[((outer * nparts + part) * (2 * MBOX + 1) + k + MBOX) * inner + i] =
-            make_double2((re[0] + re[1]) + (re[2] + re[3]), (im[0] + im[1]) + (im[2] + im[3]));
-    }
-}
-
-// acc[i] (+)= sum over parts of in[part * count + i], parts in index order
-__global__ void __launch_bounds__(256)
-lowk_parts_reduce_kernel(const double2* __restrict__ in, int nparts, int count, int accumulate, double2* __restrict__ acc) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    double re = accumulate ? acc[i].x : 0.0, im = accumulate ? acc[i].y : 0.0;
-    for (int p = 0; p < nparts; ++p) {
-        re += in[(size_t)p * count + i].x;
-        im += in[(size_t)p * count + i].y;
-    }
-    acc[i] = make_double2(re, im);
-}
-
 // modes[kx + MBOX][ky + MBOX][kz] -> sums[s] = pnorm * sum w |delta_k|^2 over the modes of shell s < MLOW (shell by
 // the binning rule in force): one thread per mode works out (shell, weighted power), then one thread per shell adds
 // its modes in index order
@@ -1480,14 +1349,13 @@ int dispatch_c2c_inv(size_t n, float2* d, const float2* tw, size_t elem_stride, 
     return launch_c2c_inv<16, 16, 16>(d, tw, elem_stride, ncols, batch, batch_stride, scale, mask, s, sb);
 }
 
+// columns per workgroup of the plain forward pass at N = 1024: 256-byte row pieces, one 1024-thread workgroup per CU with the
+// split exchange (y pass 2.02 -> 1.91 ms against 16 columns)
+constexpr int FWD_C = 32;
 template <bool POWER>
 int dispatch_c2c(size_t n, float2* d, const float2* tw, size_t elem_stride, size_t ncols, size_t batch,
                  size_t batch_stride, float scale, double* partial, hipStream_t s, const unsigned* edge_fall = nullptr, int ky0 = 0,
                  long long prune2 = 0, PackDst disc = PackDst{}, int epi_skip = 0, int no_nyq = 0, int tables = 0) {
-#ifndef FWD_C
-#define FWD_C 32                    // columns per workgroup of the plain forward pass at N = 1024: 32 = 256-byte row pieces, one 1024-thread
-                                    // workgroup per CU with the split exchange (y pass 2.02 -> 1.91 ms); 16 = as in rounds 1-2
-#endif
     if constexpr (!POWER) { if (n == 1024) return launch_c2c<32, 32, FWD_C, false>(d, tw, elem_stride, ncols, batch, batch_stride, scale, partial, s, edge_fall, ky0, prune2); }
     if (n == 1024) return launch_c2c<32, 32, 16, POWER>(d, tw, elem_stride, ncols, batch, batch_stride, scale, partial, s, edge_fall, ky0, prune2, disc, epi_skip, no_nyq, tables);
     if (n == 512) return launch_c2c<16, 32, 16, POWER>(d, tw, elem_stride, ncols, batch, batch_stride, scale, partial, s, edge_fall, ky0, prune2, disc, epi_skip, no_nyq, tables);
@@ -1913,9 +1781,9 @@ static int lowk_modes(const float* planes, const float* rec, int window, int n, 
     else if (n == 512) z(std::integral_constant<int, 8>{});
     else z(std::integral_constant<int, 4>{});
     const size_t lds = (size_t)n * sizeof(double2);
-    lowk_axis_kernel<<<dim3((unsigned)nx, 1), 256, lds, s>>>(lowz, n, n, 0, MBOX + 1, lowy);
+    lowk_axis_kernel<MBOX><<<dim3((unsigned)nx, 1), 256, lds, s>>>(lowz, n, n, 0, MBOX + 1, lowy);
     const int inner = (2 * MBOX + 1) * (MBOX + 1);
-    lowk_axis_kernel<<<dim3(1, LOWK_XPARTS), 256, lds, s>>>(lowy, n, nx, x0, inner, parts);
+    lowk_axis_kernel<MBOX><<<dim3(1, LOWK_XPARTS), 256, lds, s>>>(lowy, n, nx, x0, inner, parts);
     lowk_parts_reduce_kernel<<<(unsigned)((LOWK_MODES + 255) / 256), 256, 0, s>>>(parts, LOWK_XPARTS, (int)LOWK_MODES, accumulate, modes);
     AST_CHECK_LAUNCH();
     return AST_OK;
@@ -2064,7 +1932,7 @@ extern "C" int ast_lowk_shell_count(void) { return MLOW; }
 extern "C" int ast_lowk_modes(const void* planes, int dtype, size_t n, size_t x0, size_t nx, int accumulate, void* modes,
                               void* work, size_t work_bytes, void* stream) {
     AST_CHECK_ARG(planes && modes && work && nx >= 1 && x0 + nx <= n && (nx * n) % 4 == 0);
-    AST_CHECK_ARG(ast_fft_tile_supported(dtype, n) || (dtype == AST_F32 && n == 2048));      // (2048: the passes of lens_fft.hip's fp32 section)
+    AST_CHECK_ARG(ast_fft_tile_supported(dtype, n) || (dtype == AST_F32 && n == 2048));      // (2048: the fp32 passes of cube_fft.hip)
     AST_CHECK_ARG(work_bytes >= ast_lowk_work_bytes(n, nx));
     hipStream_t s = ast::as_stream(stream);
     AST_PROF("fft_tile.lowk", s);

@@ -1054,9 +1054,9 @@ HIDDEN_STATE = [
            filled_by="LowkLaneCache", no_clear=_FRESH),
     Hidden("csrc/fft_tile.hip", "g_side", "low-k side stream and event pair per (device, caller stream)", "per_stream",
            no_clear=_FRESH),
-    Hidden("csrc/lens_fft.hip", "g_tw", "float64 twiddle tables per (device, length)", "built_synchronously",
+    Hidden("csrc/fft_three_stage.h", "g_tw", "float64 twiddle tables per (device, length)", "built_synchronously",
            filled_by="TwCache", no_clear=_FRESH),
-    Hidden("csrc/lens_fft.hip", "g_tw32", "fp32 twiddle tables per (device, length)", "built_synchronously",
+    Hidden("csrc/cube_fft.hip", "g_tw32", "fp32 twiddle tables per (device, length)", "built_synchronously",
            filled_by="TwCache32", no_clear=_FRESH),
     # ---- C: plans, streams, communicators
     Hidden("csrc/kappa.hip", "g_host_plan", "the lens plan of the libglsg-compatible host entries", "explicit_object",
@@ -1082,4 +1082,5 @@ HIDDEN_STATE = [
 ] + [Hidden("csrc/" + f, n, "PerDeviceOnce: the kernel's dynamic-LDS limit was raised on this device", "host_only", no_clear=_ONCE)
      for f, n in (("fft_tile.hip", "attr_once"), ("pairwise_pdf.hip", "attr_once"), ("tpcf.hip", "attr_once"),
                   ("power_bin.hip", "attr_once"), ("power_bin_2d.hip", "attr_once"), ("mesh_paint_tiled.hip", "attr_once"),
-                  ("kappa.hip", "y_once"), ("lens_fft.hip", "once"))]
+                  ("kappa.hip", "y_once"), ("lens_fft.hip", "once"), ("cube_fft.hip", "once"),
+                  ("fft_three_stage.h", "once"))]

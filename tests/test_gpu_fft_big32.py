@@ -1,4 +1,4 @@
-"""The single-precision three-stage passes for cubes of side 2048 (csrc/lens_fft.hip, ast_fft32_big_power_3d): the same
+"""The single-precision three-stage passes for cubes of side 2048 (csrc/cube_fft.hip, ast_fft32_big_power_3d): the same
 kernels at side 256 against the CPU oracle and the fp32 tile pipeline; side 2048 itself against the double-precision
 passes in tests/test_gpu_fullsize.py.  Tolerance: north_star's 1e-6 relative on every shell; mode counts exact."""
 import numpy as np

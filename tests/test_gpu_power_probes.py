@@ -169,7 +169,7 @@ def test_fused_float32_variants(dev, fields, n, var, value):
     _run(f"fused f32 {var}={value}", fields, n, "f32", sums)
 
 
-# ---------------------------------------------------------------- double-precision passes and the big fp32 passes (lens_fft.hip)
+# ---------------------------------------------------------------- double-precision passes and the big fp32 passes (cube_fft.hip)
 @pytest.mark.parametrize("n", [128, 256, 512, 1024])
 def test_fused_float64(dev, fields, n):
     g = fields.grid(n, "f64")
