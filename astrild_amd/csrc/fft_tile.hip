@@ -127,7 +127,8 @@ __global__ void tile_isqrt_table_kernel(int* out, int count) {
 // A shell of radius N/4 moves 40 % of the full transform's bytes.
 struct ShellMask { const float2* src; long long lo2, hi2; int ky0 = 0; int pass = 0;       // ky0 (POWER): global k_y index of batch 0 (slab blocks)
                    size_t src_elem_stride = 0, src_batch_stride = 0;                       // strides of `src` when they differ from the destination's (0: the same)
-                   int epi_skip = 0, no_nyq = 0; };        // POWER: the epilogue skips wave steps beyond the sphere / the tile of column N/2 counts as pruned (the k_y pass left it out)
+                   int epi_skip = 0, no_nyq = 0;           // POWER: the epilogue skips wave steps beyond the sphere / the tile of column N/2 counts as pruned (the k_y pass left it out)
+                   int ysh = 0; };                         // POWER, y split (below): batch b holds k_y = (b >> ysh) + 16 * (b mod 2^ysh); 0: k_y = b + ky0
 
 // PACK: the stores go to `pack.out` in the layout the slab transpose sends (what ast_slab_pack makes of the array): row
 // k_y of batch (plane) b lands in part k_y / c1 at ((part * nbatch + b) * c1 + k_y % c1) * pitch + column.
@@ -138,6 +139,19 @@ struct ShellMask { const float2* src; long long lo2, hi2; int ky0 = 0; int pass 
 constexpr int SHELL_BATCH = 8;
 #ifndef XPASS_ATOMICS
 #define XPASS_ATOMICS 1             // perf experiments on the binning epilogue's ds_add_f64 (scripts/perf_xpass_variants.py): 0 = none, 2 = lane-unique addresses
+#endif
+// Y SPLIT (forward power pipeline): N = 16 * S.  The z pass takes its 16 rows S apart in y and does the
+// radix-16 stage of the y transform on them before it stores (rows_r2c_kernel<.., YS>): row k1 * S + y2 of a plane holds
+// A[k1] w_N^(y2 k1).  The k_y pass is then an S-point transform of the S consecutive rows of block k1 (YS = N below: the
+// kernel's own N is S, batch = plane * 16 + k1), and row b of a plane ends up holding k_y = (b / S) + 16 * (b mod S) - a
+// fixed permutation nobody undoes: the last pass only needs k_y for the pruning, the norm and the edge word.
+// Perf experiments (scripts/perf_ysplit_variants.py): columns per workgroup of the S-point pass, and the z pass's
+// epilogue mapping (0: one k_z per thread; 1: a (k_z, N/2 - k_z) pair on half of the threads).
+#ifndef YSPLIT_C
+#define YSPLIT_C 32
+#endif
+#ifndef YSPLIT_EPI_PAIRS
+#define YSPLIT_EPI_PAIRS 0
 #endif
 struct ShellBatch { int count = 0; float2* work[SHELL_BATCH]; long long lo2[SHELL_BATCH], hi2[SHELL_BATCH]; };
 struct C2RBatch { int count = 0; const float2* in[SHELL_BATCH]; float* out[SHELL_BATCH]; int kmax[SHELL_BATCH]; };
@@ -154,7 +168,7 @@ struct PackDst { float2* out = nullptr; unsigned c1_log2 = 0; unsigned nbatch = 
                  const DiscEntry* disc = nullptr; const unsigned short* gk = nullptr; unsigned part = 0;
                  unsigned xmajor = 0; };     // xmajor = N (one part only): element (x, row, col) of a tile at (row_pos * N + x) * 16 + col - the last pass reads N * 128 contiguous bytes
 
-template <int R1, int R2, int C, bool POWER, bool INV = false, int PACK = 0, bool TAB = false>      // TAB (POWER): one shell table per column lane
+template <int R1, int R2, int C, bool POWER, bool INV = false, int PACK = 0, bool TAB = false, int YS = 0>      // TAB (POWER): one shell table per column lane; YS: side of the y split
 __global__ void __launch_bounds__(C * (R1 > R2 ? R1 : R2))
 // N = 1024 with binning: 128 VGPRs, so that two 8-wave workgroups fit a CU (see SPLIT below)
 __attribute__((amdgpu_waves_per_eu((POWER || C > 16) && R1 * R2 >= 1024 ? 4 : 1, (POWER || C > 16) && R1 * R2 >= 1024 ? 4 : 8)))
@@ -165,6 +179,8 @@ strided_c2c_kernel(float2* __restrict__ data, const float2* __restrict__ tw_g, s
     constexpr int N = R1 * R2;
     constexpr int NT = C * (R1 > R2 ? R1 : R2);
     constexpr int NB = N / 2 - 1;    // shells when POWER
+    constexpr int SIDE = YS != 0 ? YS : N;                   // the transform this pass belongs to (streaming accesses, pruning)
+    static_assert(YS == 0 || (YS == 16 * N && !POWER && !INV && PACK == 0), "y split: the remaining S-point forward pass");
     // SPLIT (N = 1024, binning pass): the stage-1 -> stage-2 exchange goes through LDS in two rounds, so the
     // buffer is 64 KB instead of 128 KB and TWO workgroups fit a CU: with one, the loads, the two register
     // FFTs and the binning of a tile run strictly one after the other (x pass 1.83 -> 1.54 ms).  The y pass
@@ -209,6 +225,8 @@ strided_c2c_kernel(float2* __restrict__ data, const float2* __restrict__ tw_g, s
     const float2* disc_base = nullptr;
     unsigned disc_S = 0;
     int disc_ky = 0;
+    // (y split: the k_y this batch row holds; uniform)
+    const unsigned bky = (!INV && POWER && mask.ysh != 0) ? (b >> mask.ysh) + ((b & ((1u << mask.ysh) - 1u)) << 4) : b;
     if (!INV && POWER && pack.disc != nullptr) {
         const unsigned subb = b % R1, gk = pack.gk[pack.part * (pack.nbatch / R1) + b / R1];
         const DiscEntry e = pack.disc[(size_t)tile * R2 + gk];
@@ -226,7 +244,7 @@ strided_c2c_kernel(float2* __restrict__ data, const float2* __restrict__ tw_g, s
             disc_S = e.S;
         }
     } else if (!INV && POWER && (mask.hi2 > 0 || mask.no_nyq)) {
-        const long long kyi = (long long)b + mask.ky0, ky = kyi > N / 2 ? kyi - N : kyi;
+        const long long kyi = (long long)bky + mask.ky0, ky = kyi > N / 2 ? kyi - N : kyi;
         // (no_nyq: of the tile that starts at column N/2 only the workgroup of k_y = 0 is not pruned anyway, and none of
         // its modes - norm N/2 and up - is ever binned; the k_y pass has not transformed that column)
         if ((mask.hi2 > 0 && ky * ky + (long long)(c0 * c0) > mask.hi2) || (mask.no_nyq && c0 >= (size_t)(N / 2))) {
@@ -285,7 +303,7 @@ strided_c2c_kernel(float2* __restrict__ data, const float2* __restrict__ tw_g, s
             }
         } else {
 #pragma unroll
-            for (int n1 = 0; n1 < R1; ++n1) v[n1] = ld_stream<(!INV && N >= 1024)>(ubase + (size_t)(n1 * R2) * es_in + voff);
+            for (int n1 = 0; n1 < R1; ++n1) v[n1] = ld_stream<(!INV && SIDE >= 1024)>(ubase + (size_t)(n1 * R2) * es_in + voff);
         }
         if (INV) {
             if (mask.hi2 > 0 && mask.pass == 0) {
@@ -406,6 +424,14 @@ strided_c2c_kernel(float2* __restrict__ data, const float2* __restrict__ tw_g, s
                 float2 x = u[bitrev(k2, ilog2(R2))];
                 x.x *= scale;
                 x.y *= INV ? -scale : scale;
+                if (YS != 0) {
+                    // y split: row sub + R1 k2 of block k1 = b mod 16 holds k_y = k1 + 16 (sub + R1 k2); the parent's rule on
+                    // that index, per lane (this small pass has the registers): exactly the rows inside the disc are stored
+                    const int kyn = (int)(b & 15u) + 16 * (sub + R1 * k2), ky = kyn > SIDE / 2 ? kyn - SIDE : kyn;
+                    if (ky * ky > room) continue;
+                    st_stream<(SIDE >= 1024)>(base + (size_t)(sub + R1 * k2) * elem_stride, x);
+                    continue;
+                }
                 if (!INV) {
                     const int aky = R1 * k2 >= N / 2 ? N - (wsub1 + R1 * k2) : wsub0 + R1 * k2;    // smallest |k_y| in the wave
                     if (aky * aky > room) continue;
@@ -433,8 +459,8 @@ strided_c2c_kernel(float2* __restrict__ data, const float2* __restrict__ tw_g, s
         // (the word is fetched HERE, not at the top: nothing of this epilogue may stay live across the two register
         // FFTs - the kernel is held to 128 VGPRs and every long-lived value there turned into scratch traffic)
         unsigned fallmask = 0;
-        const int kyi = disc_base != nullptr ? disc_ky : (int)b + mask.ky0;
-        if (edge_fall) fallmask = edge_fall[((size_t)(disc_base != nullptr ? (unsigned)disc_ky : b) * tiles_per_batch + tile) * NT + threadIdx.x];
+        const int kyi = disc_base != nullptr ? disc_ky : (int)bky + mask.ky0;
+        if (edge_fall) fallmask = edge_fall[((size_t)(disc_base != nullptr ? (unsigned)disc_ky : bky) * tiles_per_batch + tile) * NT + threadIdx.x];
         const int kz = (int)c0 + tid_e % C;
         const int ky = kyi > N / 2 ? kyi - N : kyi;
         const int m2yz = ky * ky + kz * kz;
@@ -622,34 +648,53 @@ __device__ inline void real_dft_low7(const double (&f)[R1], Emit&& emit) {
 // periodic grid, every row folded.
 struct SlabFold { int xb0 = 0, ntx = 0, row_lo = 0, row_hi = 0; bool ranges = false; };      // ranges: plane ranges of a buffer (ntx = 0: the periodic grid)
 
-template <int R1, int R2, int C, int FOLDW, bool LOWK = false>
+// YS (y split, see above; the whole periodic grid, nrows = N * N): workgroup (x, y2) takes the 16 rows y2 + S j of plane x,
+// S = N / 16 - which 16 rows a workgroup holds is free - and, after the even/odd split, runs the radix-16 stage of the y
+// transform over them for every k_z: A[k1] = sum_j X_j w_16^(j k1), times w_N^(y2 k1) from the twiddle table in LDS, stored
+// to row k1 S + y2 of the plane, contiguous along k_z like before.  No extra byte of memory traffic.  `ycols` columns are
+// written: N/2, or N/2 + 1 when the route keeps column N/2.  The fold and the low-k sums go by the rows' true indices;
+// all 16 rows share y mod 8, so the fold's branch is uniform over the workgroup.
+// Which y2 workgroup i of a plane takes (i, y2 < S, S a multiple of 8): the low three bits rotated by i / 8.  Workgroups go
+// round-robin to the 8 XCDs and S is a multiple of 8, so with y2 = i every workgroup whose rows carry the fold's y-records
+// (y mod 8 = 0; TSC: 7 as well) - twice the loads of the others - landed on XCD 0: z pass 1.83 -> 2.10 ms on a deferred-fold
+// grid where the plain grid gained.  Rotated, a plane's eight such workgroups go to eight XCDs.
+template <int S>
+__device__ inline unsigned ysplit_y2(unsigned blk) {
+    static_assert(S % 8 == 0, "eight workgroups to a rotation");
+    const unsigned i = blk % (unsigned)S;
+    return (i & ~7u) | ((i + (i >> 3)) & 7u);
+}
+
+template <int R1, int R2, int C, int FOLDW, bool LOWK = false, bool YS = false>
 __global__ void __launch_bounds__(C * R2)
 __attribute__((amdgpu_waves_per_eu(LOWK ? 4 : 1, LOWK ? 4 : 8)))     // LOWK: keep two workgroups per CU (128 VGPRs)
 rows_r2c_kernel(const float* __restrict__ in, float2* __restrict__ out, const float2* __restrict__ tw_g,
                 size_t nrows, size_t in_pitch, size_t out_pitch, float scale, float mean,
                 const float* __restrict__ rec, const double2* __restrict__ lowk_lane = nullptr,
-                double* __restrict__ lowz = nullptr, SlabFold sf = SlabFold{}) {
+                double* __restrict__ lowz = nullptr, SlabFold sf = SlabFold{}, int ycols = 0) {
     constexpr int M = R1 * R2, N = 2 * M;
     constexpr int NT = C * R2;
     constexpr int R2P = R2 + 1;
     constexpr int MP = M + 1;
+    static_assert(!YS || C == 16, "y split: the workgroup's rows are the inputs of one radix-16 stage");
+    constexpr size_t RS = YS ? N / 16 : 1;                        // distance of the workgroup's rows
     extern __shared__ float2 lds[];
     float2* Y = lds;                     // stage buffer [r][k1][n2] (padded), then Z[r][k]
     float2* tw = lds + C * (R1 * R2P > MP ? R1 * R2P : MP);     // exp(-2 pi i m / N), m < N
     for (int i = threadIdx.x; i < N; i += NT) tw[i] = tw_g[i];
 
-    const size_t row0 = (size_t)blockIdx.x * C;
+    const size_t row0 = YS ? (size_t)(blockIdx.x / (unsigned)RS) * N + ysplit_y2<YS ? N / 16 : 8>(blockIdx.x) : (size_t)blockIdx.x * C;
     const int n2 = threadIdx.x % R2, r = threadIdx.x / R2;        // stage-1 task (r, n2)
     {
         // z[j] = x[2j] + i x[2j+1]; rows past the end re-read the last one (unconditional loads)
-        const float2* zin = reinterpret_cast<const float2*>(in + min(row0 + r, nrows - 1) * in_pitch);
+        const float2* zin = reinterpret_cast<const float2*>(in + min(row0 + r * RS, nrows - 1) * in_pitch);
         float2 v[R1];
         const float* src[3];
         int ns = 0;
         if (FOLDW != 0) {                    // the record lines of this row, found before any load is issued
             constexpr int W = FOLDW != 0 ? FOLDW : 2;
             const int ng = (int)(2 * M);
-            const size_t row = min(row0 + r, nrows - 1);
+            const size_t row = min(row0 + r * RS, nrows - 1);
             if (sf.ntx == 0) {
                 const int xb = sf.xb0 + (int)(row / ng), trow = xb / ast::TX;
                 ns = !sf.ranges || (trow >= sf.row_lo && trow < sf.row_hi)
@@ -744,8 +789,8 @@ rows_r2c_kernel(const float* __restrict__ in, float2* __restrict__ out, const fl
             constexpr int SH = R2 == 32 ? 1 : 0;             // the lane bits below the four that select the element
             const int sel = lane >> SH;
             const int sub = ((sel >> 2) & 1) * 4 + ((sel >> 1) & 1) * 2 + (sel & 1);
-            if ((R2 == 16 || (lane & 1) == 0) && sub < 7 && row0 + r < nrows)
-                lowz[(row0 + r) * (size_t)(2 * (MBOX_FWD + 1)) + ((sel >> 3) & 1) * 7 + sub] = acc[0];
+            if ((R2 == 16 || (lane & 1) == 0) && sub < 7 && row0 + r * RS < nrows)
+                lowz[(row0 + r * RS) * (size_t)(2 * (MBOX_FWD + 1)) + ((sel >> 3) & 1) * 7 + sub] = acc[0];
         }
 #pragma unroll
         for (int n1 = 0; n1 < R1; ++n1) {
@@ -777,6 +822,72 @@ rows_r2c_kernel(const float* __restrict__ in, float2* __restrict__ out, const fl
     }
     __syncthreads();
     // even/odd split: X[k] = (Zk + conj(Zm))/2 - i w^k (Zk - conj(Zm))/2, m = M - k, w = e^{-2 pi i / N}
+    if constexpr (YS) {
+        constexpr int S = N / 16;
+        const unsigned y2 = ysplit_y2<S>(blockIdx.x);
+        float2* const obase = out + ((size_t)(blockIdx.x / (unsigned)S) * N + y2) * out_pitch;
+        // the radix-16 stage over the workgroup's rows at column k, twiddle, 16 stores (a wave: 512 contiguous bytes each)
+        auto stage_y = [&](float2 (&x)[16], int k) __attribute__((always_inline)) {
+            fft_reg<16>(x);
+#pragma unroll
+            for (int k1 = 0; k1 < 16; ++k1) {
+                float2 a = x[bitrev(k1, 4)];
+                // (a uniform index: from the table in memory these are scalar loads into scalar registers - read from the
+                // copy in LDS the 15 factors took 30 of the 128 VGPRs and the epilogue spilled)
+                if (k1 != 0) a = cmul(a, tw_g[y2 * k1]);
+                // (a uniform base per row plus the 32-bit column as the lane offset: no 64-bit lane address per store)
+                float2* const ub = obase + (size_t)(k1 * S) * out_pitch;
+                st_stream<(N >= 1024)>(ub + (uint32_t)k, a);
+            }
+        };
+#if YSPLIT_EPI_PAIRS
+        // thread k <= M/2 forms X[k] and X[M-k] of every row from one pair of reads, as the plain epilogue does
+        static_assert(!YS || NT >= M, "a thread per column");
+        if (const int k = threadIdx.x; k <= M / 2) {
+            const float2 w = tw[k];
+            float2 xa[16], xb[16];
+#pragma unroll
+            for (int rr = 0; rr < 16; ++rr) {
+                const float2 zk = Y[rr * MP + k];
+                const float2 zm = Y[rr * MP + ((M - k) & (M - 1))];
+                const float2 e = make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y));
+                const float2 o = make_float2(0.5f * (zk.x - zm.x), 0.5f * (zk.y + zm.y));
+                const float2 t = cmul(o, w);
+                xa[rr] = make_float2((e.x + t.y) * scale, (e.y - t.x) * scale);
+                xb[rr] = make_float2((e.x - t.y) * scale, (-e.y - t.x) * scale);
+                if (k == 0) {
+                    xa[rr] = make_float2((zk.x + zk.y) * scale, 0.f);
+                    xb[rr] = make_float2((zk.x - zk.y) * scale, 0.f);
+                }
+            }
+            stage_y(xa, k);
+            if (k != M / 2 && M - k < ycols) stage_y(xb, M - k);
+        }
+#else
+        // one column per thread (no loop: the stores keep their uniform bases), k < ycols <= M + 1 - thread 0 also takes
+        // column M when it is kept: the formula above holds for every k with Z[M] = Z[0]
+        static_assert(!YS || NT >= M, "a thread per column");
+        auto column = [&](int k) __attribute__((always_inline)) {
+            const int ka = k & (M - 1), km = (M - k) & (M - 1);
+            const float2 w = tw[k];
+            float2 x[16];
+#pragma unroll
+            for (int rr = 0; rr < 16; ++rr) {
+                const float2 zk = Y[rr * MP + ka];
+                const float2 zm = Y[rr * MP + km];
+                const float2 e = make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y));
+                const float2 o = make_float2(0.5f * (zk.x - zm.x), 0.5f * (zk.y + zm.y));
+                const float2 t = cmul(o, w);
+                x[rr] = make_float2((e.x + t.y) * scale, (e.y - t.x) * scale);
+                if (ka == 0) x[rr] = make_float2((k == 0 ? zk.x + zk.y : zk.x - zk.y) * scale, 0.f);     // X[0], X[M]: real
+            }
+            stage_y(x, k);
+        };
+        if ((int)threadIdx.x < M) column((int)threadIdx.x);
+        if (ycols > M && threadIdx.x == 0) column(M);
+#endif
+        return;
+    }
     for (int i = threadIdx.x; i < C * (M / 2 + 1); i += NT) {
         const int rr = i / (M / 2 + 1), k = i % (M / 2 + 1);
         if (row0 + rr >= nrows) continue;
@@ -1271,7 +1382,7 @@ struct TwiddleCache {
 template <int R1, int R2, int C, bool POWER>
 int launch_c2c(float2* data, const float2* tw, size_t elem_stride, size_t ncols, size_t batch, size_t batch_stride,
                float scale, double* partial, hipStream_t s, const unsigned* edge_fall = nullptr, int ky0 = 0, long long prune2 = 0,
-               PackDst disc = PackDst{}, int epi_skip = 0, int no_nyq = 0, int tables = 0) {
+               PackDst disc = PackDst{}, int epi_skip = 0, int no_nyq = 0, int tables = 0, int ysh = 0) {
     constexpr int N = R1 * R2, NT = C * (R1 > R2 ? R1 : R2);
     constexpr bool SPLIT = (POWER || C > 16) && R1 == R2 && N * C * sizeof(float2) > 64 * 1024;       // as in the kernel
     const size_t lds = (size_t)((SPLIT ? N / 2 : N) * C + N) * sizeof(float2) + (POWER ? (N / 2) * sizeof(double) : 0);
@@ -1289,6 +1400,7 @@ int launch_c2c(float2* data, const float2* tw, size_t elem_stride, size_t ncols,
     ShellMask mask{nullptr, 0, prune2, ky0};
     mask.epi_skip = epi_skip;
     mask.no_nyq = no_nyq;
+    mask.ysh = ysh;
     if (POWER && tables)
         strided_c2c_kernel<R1, R2, C, POWER, false, 0, POWER><<<(unsigned)(tiles * batch), NT, lds, s>>>(data, tw, elem_stride, ncols,
                                                                                                        batch_stride, (unsigned)tiles, scale,
@@ -1355,30 +1467,45 @@ constexpr int FWD_C = 32;
 template <bool POWER>
 int dispatch_c2c(size_t n, float2* d, const float2* tw, size_t elem_stride, size_t ncols, size_t batch,
                  size_t batch_stride, float scale, double* partial, hipStream_t s, const unsigned* edge_fall = nullptr, int ky0 = 0,
-                 long long prune2 = 0, PackDst disc = PackDst{}, int epi_skip = 0, int no_nyq = 0, int tables = 0) {
+                 long long prune2 = 0, PackDst disc = PackDst{}, int epi_skip = 0, int no_nyq = 0, int tables = 0, int ysh = 0) {
     if constexpr (!POWER) { if (n == 1024) return launch_c2c<32, 32, FWD_C, false>(d, tw, elem_stride, ncols, batch, batch_stride, scale, partial, s, edge_fall, ky0, prune2); }
-    if (n == 1024) return launch_c2c<32, 32, 16, POWER>(d, tw, elem_stride, ncols, batch, batch_stride, scale, partial, s, edge_fall, ky0, prune2, disc, epi_skip, no_nyq, tables);
-    if (n == 512) return launch_c2c<16, 32, 16, POWER>(d, tw, elem_stride, ncols, batch, batch_stride, scale, partial, s, edge_fall, ky0, prune2, disc, epi_skip, no_nyq, tables);
-    return launch_c2c<16, 16, 16, POWER>(d, tw, elem_stride, ncols, batch, batch_stride, scale, partial, s, edge_fall, ky0, prune2, disc, epi_skip, no_nyq, tables);
+    if (n == 1024) return launch_c2c<32, 32, 16, POWER>(d, tw, elem_stride, ncols, batch, batch_stride, scale, partial, s, edge_fall, ky0, prune2, disc, epi_skip, no_nyq, tables, ysh);
+    if (n == 512) return launch_c2c<16, 32, 16, POWER>(d, tw, elem_stride, ncols, batch, batch_stride, scale, partial, s, edge_fall, ky0, prune2, disc, epi_skip, no_nyq, tables, ysh);
+    return launch_c2c<16, 16, 16, POWER>(d, tw, elem_stride, ncols, batch, batch_stride, scale, partial, s, edge_fall, ky0, prune2, disc, epi_skip, no_nyq, tables, ysh);
 }
 
-template <int R1, int R2, int C, int FOLDW = 0, bool LOWK = false>
+// y split: the S-point k_y pass, S = n / 16 = R1 * R2 (tw: the S-entry table), in place on the 16 n blocks of S consecutive rows
+template <int R1, int R2, int C, int SIDE>
+int launch_c2c_ysplit(float2* data, const float2* tw, size_t pitch, size_t ncols, long long prune2, hipStream_t s) {
+    constexpr int S = R1 * R2, NT = C * (R1 > R2 ? R1 : R2);
+    static_assert(16 * S == SIDE, "one radix-16 stage was done by the z pass");
+    const size_t lds = (size_t)(S * C + S) * sizeof(float2);                    // (at most 33 KB: no attribute to set)
+    const size_t tiles = (ncols + C - 1) / C, batch = (size_t)16 * SIDE;
+    AST_CHECK_ARG(tiles * batch < 0x7fffffffull);
+    AST_CHECK_ARG((size_t)(R2 - 1) * pitch + ncols < (1ull << 29));             // the kernel's 32-bit lane offsets
+    strided_c2c_kernel<R1, R2, C, false, false, 0, false, SIDE><<<(unsigned)(tiles * batch), NT, lds, s>>>(
+        data, tw, pitch, ncols, (size_t)S * pitch, (unsigned)tiles, 1.0f, nullptr, nullptr, ShellMask{nullptr, 0, prune2});
+    AST_CHECK_LAUNCH();
+    return AST_OK;
+}
+
+template <int R1, int R2, int C, int FOLDW = 0, bool LOWK = false, bool YS = false>
 int launch_r2c(const float* in, float2* out, const float2* tw, size_t nrows, size_t in_pitch, size_t out_pitch,
                float scale, float mean, hipStream_t s, const float* rec = nullptr, const double2* lowk_lane = nullptr,
-               double* lowz = nullptr, SlabFold sf = SlabFold{}) {
+               double* lowz = nullptr, SlabFold sf = SlabFold{}, int ycols = 0) {
     constexpr int M = R1 * R2, N = 2 * M, NT = C * R2;
     constexpr int BUF = C * (R1 * (R2 + 1) > M + 1 ? R1 * (R2 + 1) : M + 1);
     const size_t lds = (size_t)(BUF + N) * sizeof(float2);
     static ast::PerDeviceOnce attr_once;
     if (attr_once.need()) {
-        AST_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&rows_r2c_kernel<R1, R2, C, FOLDW, LOWK>),
+        AST_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&rows_r2c_kernel<R1, R2, C, FOLDW, LOWK, YS>),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         attr_once.mark();
     }
     const size_t blocks = (nrows + C - 1) / C;
     AST_CHECK_ARG(blocks < 0x7fffffffull);
-    rows_r2c_kernel<R1, R2, C, FOLDW, LOWK><<<(unsigned)blocks, NT, lds, s>>>(in, out, tw, nrows, in_pitch, out_pitch, scale, mean, rec,
-                                                                             lowk_lane, lowz, sf);
+    rows_r2c_kernel<R1, R2, C, FOLDW, LOWK, YS><<<(unsigned)blocks, NT, lds, s>>>(in, out, tw, nrows, in_pitch, out_pitch, scale, mean, rec,
+                                                                                 lowk_lane, lowz, sf, ycols);
     AST_CHECK_LAUNCH();
     return AST_OK;
 }
@@ -1592,7 +1719,7 @@ struct LowkLaneCache {
 
 static int rows_r2c_impl(const void* in, void* out, int dtype, size_t n, size_t nrows, size_t in_pitch,
                          size_t out_pitch, double scale, double mean, void* stream, const void* rec = nullptr,
-                         int window = 0, double* lowz = nullptr, SlabFold sf = SlabFold{}) {
+                         int window = 0, double* lowz = nullptr, SlabFold sf = SlabFold{}, int ycols = 0) {
     AST_CHECK_ARG(in != nullptr && out != nullptr && in != out && nrows >= 1);
     AST_CHECK_ARG(ast_fft_tile_supported(dtype, n));
     AST_CHECK_ARG(in_pitch >= n && in_pitch % 2 == 0 && out_pitch >= n / 2 + 1);
@@ -1604,6 +1731,28 @@ static int rows_r2c_impl(const void* in, void* out, int dtype, size_t n, size_t 
     AST_PROF("fft_tile.rows_r2c", s);
     const float* i = (const float*)in;
     float2* o = (float2*)out;
+    if (ycols != 0) {                        // y split (power_3d_impl): the whole periodic grid, ycols columns written
+        AST_CHECK_ARG(nrows == n * n && in_pitch == n && !sf.ranges && (ycols == (int)(n / 2) || ycols == (int)(n / 2 + 1)));
+        AST_CHECK_ARG(rec == nullptr || window == AST_WIN_CIC || window == AST_WIN_TSC);
+        const double2* lane = lowz != nullptr ? g_lowk_lane.get((int)n, s) : nullptr;
+        if (lowz != nullptr && !lane) { ast::set_error("ast_fft_tile_rows_r2c: low-k lane table allocation failed"); return AST_ERR_HIP; }
+        const float* h = (const float*)rec;
+        const float sc = (float)scale, mn = (float)mean;
+        auto go = [&](auto r1, auto r2) {
+            constexpr int R1 = decltype(r1)::value, R2 = decltype(r2)::value;
+            auto fw = [&](auto foldw) {
+                constexpr int FW = decltype(foldw)::value;
+                if (lowz != nullptr) return launch_r2c<R1, R2, 16, FW, true, true>(i, o, tw, nrows, in_pitch, out_pitch, sc, mn, s, h, lane, lowz, sf, ycols);
+                return launch_r2c<R1, R2, 16, FW, false, true>(i, o, tw, nrows, in_pitch, out_pitch, sc, mn, s, h, nullptr, nullptr, sf, ycols);
+            };
+            if (rec == nullptr) return fw(std::integral_constant<int, 0>{});
+            if (window == AST_WIN_CIC) return fw(std::integral_constant<int, 2>{});
+            return fw(std::integral_constant<int, 3>{});
+        };
+        if (n == 1024) return go(std::integral_constant<int, 16>{}, std::integral_constant<int, 32>{});
+        if (n == 512) return go(std::integral_constant<int, 16>{}, std::integral_constant<int, 16>{});
+        return go(std::integral_constant<int, 8>{}, std::integral_constant<int, 16>{});
+    }
     if (lowz != nullptr) {                   // with the low-k channel's z sums on the side
         const double2* lane = g_lowk_lane.get((int)n, s);
         if (!lane) { ast::set_error("ast_fft_tile_rows_r2c: low-k lane table allocation failed"); return AST_ERR_HIP; }
@@ -1850,8 +1999,16 @@ static int power_3d_impl(const void* grid, void* scratch, size_t scratch_bytes, 
         if (!side) { ast::set_error("ast_fft_tile_power_3d: side stream creation failed"); return AST_ERR_HIP; }
         if (!z_fused) { const int rc = lowk_rest(); if (rc != AST_OK) return rc; }
     }
+    // Y SPLIT: the z pass does the first radix-16 stage of the y transform, the k_y pass the remaining n/16 points on
+    // small tiles; rows come out permuted and the last pass reads k_y off the row index.  Default at side 1024
+    // (AST_FFT_YSPLIT=0: the passes as they were); AST_FFT_YSPLIT=1 takes it at sides 256 and 512 too.
+    const char* ys_env = getenv("AST_FFT_YSPLIT");
+    const bool ysplit = !disc_asked && (ys_env != nullptr ? ys_env[0] == '1' : n == 1024);
+    int ysh = 0;
+    if (ysplit) for (size_t v = n / 16; v > 1; v >>= 1) ++ysh;
     int rc = rows_r2c_impl(grid, spec, dtype, n, n * n, n, nzp, 1.0, mean, stream, rec, window,
-                           z_fused ? reinterpret_cast<double*>(work) : nullptr);                       // z
+                           z_fused ? reinterpret_cast<double*>(work) : nullptr, SlabFold{},
+                           ysplit ? (int)(no_nyq ? n / 2 : nz) : 0);                                   // z
     if (rc != AST_OK) return rc;
     if (z_fused) { rc = lowk_rest(); if (rc != AST_OK) return rc; }
     // both strided passes leave out what FFTPower drops: rows / tiles with k_y^2 + k_z0^2 > (n/2)^2 (AST_FFT_NO_PRUNE: A/B runs)
@@ -1896,7 +2053,15 @@ static int power_3d_impl(const void* grid, void* scratch, size_t scratch_bytes, 
     } else {
         {
             AST_PROF("fft_tile.c2c", s);
-            rc = dispatch_c2c<false>(n, spec, tw, nzp, no_nyq ? n / 2 : nz, n, n * nzp, 1.0f, nullptr, s, nullptr, 0, prune2);       // y, per x-plane
+            if (ysplit) {
+                const float2* tws = g_tw.get((int)(n / 16));
+                if (!tws) { ast::set_error("ast_fft_tile_power_3d: twiddle table allocation failed"); return AST_ERR_HIP; }
+                const size_t yc = no_nyq ? n / 2 : nz;
+                if (n == 1024) rc = launch_c2c_ysplit<8, 8, YSPLIT_C, 1024>(spec, tws, nzp, yc, prune2, s);
+                else if (n == 512) rc = launch_c2c_ysplit<4, 8, YSPLIT_C, 512>(spec, tws, nzp, yc, prune2, s);
+                else rc = launch_c2c_ysplit<4, 4, YSPLIT_C, 256>(spec, tws, nzp, yc, prune2, s);
+            } else
+                rc = dispatch_c2c<false>(n, spec, tw, nzp, no_nyq ? n / 2 : nz, n, n * nzp, 1.0f, nullptr, s, nullptr, 0, prune2);       // y, per x-plane
             if (rc != AST_OK) return rc;
         }
         AST_PROF("fft_tile.c2c_power", s);
@@ -1905,7 +2070,7 @@ static int power_3d_impl(const void* grid, void* scratch, size_t scratch_bytes, 
             edge_fall = g_edge.get(n, boxsize, s);
             if (!edge_fall) { ast::set_error("ast_fft_tile_power_3d: edge table allocation failed"); return AST_ERR_HIP; }
         }
-        rc = dispatch_c2c<true>(n, spec, tw, n * nzp, nz, n, nzp, (float)inv_ng, partial, s, edge_fall, 0, prune2, PackDst{}, epi_skip, no_nyq, tables);   // x + binning
+        rc = dispatch_c2c<true>(n, spec, tw, n * nzp, nz, n, nzp, (float)inv_ng, partial, s, edge_fall, 0, prune2, PackDst{}, epi_skip, no_nyq, tables, ysh);   // x + binning
         if (rc != AST_OK) return rc;
     }
     AST_PROF("fft_tile.shell_reduce", s);
