@@ -232,6 +232,9 @@ SIGNATURES = {
     "ast_plane_paint_accumulate": (_i, [_i, _i, _i, _vp, _vp, _sz, _sz, _i, _i, _i, _d, _d, _d, ct.POINTER(_d), _vp, _d, _d,
                                         _vp, _vp, _vp]),
     "ast_plane_paint_finish": (_i, [_i, _i, _vp, _vp, _vp, _i, _i, _d, _vp, _vp]),
+    "ast_lens_green_multiply": (_i, [_vp, _i, _d, _vp]),
+    "ast_ray_step": (_i, [_vp, _i, _vp, _i, _d, _d, _d, _i, _vp]),
+    "ast_ray_emit": (_i, [_vp, _i, _d, _d, _vp, _sz, _vp]),
 }
 
 _lib = None

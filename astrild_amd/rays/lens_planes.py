@@ -15,13 +15,14 @@ of that plane holds at the mean density: ``rho (L / npix)^2 dchi_p`` (box), ``rh
 (chi_hi^3 - chi_lo^3) / 3`` per unit cos^-3 (cone: gnomonic pixels shrink in solid angle as cos^3 off axis, and the
 finish kernel divides that out).  Then ``kappa = sum_p W_p D_p``, ``W_p = 3/2 Omega_m D_H^-2 g(chi_p, chi_s) / a_p`` with
 g = (chi_s - chi) chi / chi_s at the plane's mid-point and 0 from chi_p >= chi_s on: the Born approximation, no
-lens-lens coupling."""
+lens-lens coupling.  ``ray_trace`` goes beyond it: multi-plane ray tracing over the same planes gives convergence, shear,
+rotation and deflection with lens-lens coupling (``astrild_amd.ray_trace``)."""
 import math
 
 import numpy as np
 import torch
 
-from .. import device as dev, lensing, plane_paint as pp
+from .. import device as dev, lensing, plane_paint as pp, ray_trace as rt
 
 D_HUBBLE = 2997.92458              # c / (100 km/s/Mpc) in Mpc/h
 SIMPSON_STEPS = 512
@@ -181,6 +182,34 @@ class LensPlanes:
         for s, z in enumerate(zs):
             lensing.kappa_stack(self.planes, *self.source_weights(z), out=out[s])
         return out
+
+    def ray_trace(self, z_src, born=False, pad=None, opening_angle=None):
+        """Multi-plane ray tracing through the resident planes (``ray_trace.trace``): a dict of float64
+        device tensors "kappa", "gamma1", "gamma2", "omega", "alpha1", "alpha2" (deflection in radians, component 1
+        along array axis 0; the lens equation is beta = theta - alpha), ``(npix, npix)`` for a scalar ``z_src`` and
+        ``(S, npix, npix)`` for a sequence, in the caller's order.  Plane k deflects with the potential of
+        ``sigma_k = chi_k 3/2 Omega_m D_H^-2 D_k / a_k`` minus its mean, solved on a periodic grid of ``pad`` times npix
+        a side with the map in one corner: ``pad`` 1 for a box (it is periodic), 2 for a cone by default.  Pixels are
+        ``opening_angle`` / npix apart (degrees: the cone's own by default; a box has none, the caller gives it).
+        ``born``: deflections and distortions are sampled along the undeflected rays and do not couple.  A source at or
+        in front of the first plane gets zeros."""
+        if self.planes is None:
+            raise ValueError("the planes are not finished: call finish() after the last add()")
+        if pad is None:
+            pad = 1 if self.geometry == "box" else 2
+        pad = rt.check_pad(pad)
+        if opening_angle is None:
+            if self.geometry != "cone":
+                raise ValueError("a box has no opening angle: pass opening_angle (degrees)")
+            opening_angle = self.opening_angle_deg
+        angle = float(opening_angle)
+        if not (math.isfinite(angle) and angle > 0.0):
+            raise ValueError(f"opening_angle must be positive and finite (degrees), got {opening_angle!r}")
+        scalar = np.ndim(z_src) == 0
+        chi_src = [flat_lcdm_comoving(float(z), self.omega_m) for z in ([z_src] if scalar else z_src)]
+        weights = 1.5 * self.omega_m * (1.0 / D_HUBBLE) ** 2 / self.a
+        maps = rt.trace(self.planes, self.chi, weights, math.radians(angle) / self.npix, chi_src, born=born, pad=pad)
+        return {name: maps[q, 0] if scalar else maps[q] for q, name in enumerate(rt.QUANTITIES)}
 
     def sky_array(self, z_src, opening_angle=None):
         """The convergence map of ONE source redshift as a ``SkyArray`` of quantity "kappa_2"; the map stays on the

@@ -1344,6 +1344,42 @@ int ast_plane_paint_accumulate(int geometry, int window, int dtype, const void* 
 int ast_plane_paint_finish(int geometry, int out_dtype, const long long* sums_d, const double* mul_d, const double* add_d,
                            int nplanes, int npix, double c1, void* out_d, void* stream);
 
+/* ------------------------------------------------------------- multi-plane ray tracing over lens planes
+ * Flat sky, angles in radians, distances comoving.  Everything is double, one rounding per written operation, no fused
+ * multiply-add; tests/ray_trace_oracle.py restates step and emit in numpy and the GPU tests compare bytes.  Nothing
+ * outlives a call; all work goes to `stream`.
+ *
+ * ast_lens_green_multiply: spec_d, the (m, m/2 + 1) interleaved complex128 half spectrum of an m x m plane (what an R2C
+ *   of ast_fft_exec leaves), in place: mode (a, b) times -2 scale / (4 (sin^2(pi a / m) + sin^2(pi b / m))), mode (0, 0)
+ *   set to 0.  After an unnormalised C2R and with scale = c h^2 / m^2 the result psi has the 5-point Laplacian
+ *   (psi[a+1,b] + psi[a-1,b] + psi[a,b+1] + psi[a,b-1] - 4 psi[a,b]) / h^2 = 2 c (plane - its mean), to rounding.
+ *
+ * ast_ray_step: one lens plane.  psi_d: (m, m), periodic.  state_d: 12 planes of (npix, npix), npix <= m, in the order
+ *   d1 d2 s1 s2 A11 A12 A21 A22 B11 B12 B21 B22 (d = beta - theta, s = dx/dchi - theta, A = d beta / d theta - I,
+ *   B = d (dx/dchi) / d theta - I; component 1 is array axis 0), updated in place.  Ray (i, j) passes node (i, j) of psi
+ *   undeflected.  With dchi = chi_k - chi_prev (formed on the host), 0 <= chi_prev < chi_k:
+ *     advance   d <- (chi_prev d + dchi s) / chi_k, A <- (chi_prev A + dchi B) / chi_k, entry by entry
+ *     position  p1 = i + d1 / h, p2 = j + d2 / h (born: p = (i, j)); a = floor(p1), fx = p1 - a, b and fy alike; node
+ *               indices wrap modulo m (floor(p) is clamped to +-2^30 first: no state reads outside psi_d)
+ *     at the nodes (a, b), (a+1, b), (a, b+1), (a+1, b+1), each written with ITS OWN a, b:
+ *               a1 = (psi[a+1,b] - psi[a-1,b]) / (2 h)            u11 = ((psi[a+1,b] - 2 psi[a,b]) + psi[a-1,b]) / (h h)
+ *               a2 = (psi[a,b+1] - psi[a,b-1]) / (2 h)            u22 = ((psi[a,b+1] - 2 psi[a,b]) + psi[a,b-1]) / (h h)
+ *               u12 = (((psi[a+1,b+1] - psi[a+1,b-1]) - psi[a-1,b+1]) + psi[a-1,b-1]) / (4 (h h))
+ *     bilinear  q = ((w00 q00 + w10 q10) + w01 q01) + w11 q11 in that node order, w00 = (1-fx)(1-fy), w10 = fx (1-fy),
+ *               w01 = (1-fx) fy, w11 = fx fy: alpha1, alpha2, U11, U22, U12 (= U21)
+ *     deflect   s <- s - alpha;  B11 <- B11 - (U11 (1 + A11) + U12 A21),  B12 <- B12 - (U11 A12 + U12 (1 + A22)),
+ *               B21 <- B21 - (U12 (1 + A11) + U22 A21),  B22 <- B22 - (U12 A12 + U22 (1 + A22));  born: B <- B - U
+ *
+ * ast_ray_emit: the maps of a source at chi_s > chi_k, chi_k the plane the state was last stepped through:
+ *   x_s = (chi_k x + (chi_s - chi_k) y) / chi_s for (x, y) = (d, s) and (A, B) entry by entry; then six planes of
+ *   (npix, npix), plane q at out_d + q out_stride (doubles): kappa = -0.5 (A11 + A22), gamma1 = -0.5 (A11 - A22),
+ *   gamma2 = -0.5 (A12 + A21), omega = 0.5 (A21 - A12), alpha1 = -d1, alpha2 = -d2.  Every element is written. */
+int ast_lens_green_multiply(void* spec_d, int m, double scale, void* stream);
+int ast_ray_step(const double* psi_d, int m, double* state_d, int npix, double h, double chi_prev, double chi_k, int born,
+                 void* stream);
+int ast_ray_emit(const double* state_d, int npix, double chi_k, double chi_s, double* out_d, size_t out_stride,
+                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif
