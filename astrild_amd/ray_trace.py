@@ -25,7 +25,7 @@ from .device import dense, ptr, stream
 
 STATE = ("d1", "d2", "s1", "s2", "A11", "A12", "A21", "A22", "B11", "B12", "B21", "B22")
 QUANTITIES = ("kappa", "gamma1", "gamma2", "omega", "alpha1", "alpha2")
-NPIX_MAX = 1 << 18                # the step kernel's launch grid: npix / 4 rows of workgroups, at most 65535
+NPIX_MAX = 4 * 65535              # the step kernel's launch grid: ceil(npix / 4) rows of workgroups, at most 65535
 
 
 def _positive(value, name):

@@ -1354,7 +1354,8 @@ int ast_plane_paint_finish(int geometry, int out_dtype, const long long* sums_d,
  *   set to 0.  After an unnormalised C2R and with scale = c h^2 / m^2 the result psi has the 5-point Laplacian
  *   (psi[a+1,b] + psi[a-1,b] + psi[a,b+1] + psi[a,b-1] - 4 psi[a,b]) / h^2 = 2 c (plane - its mean), to rounding.
  *
- * ast_ray_step: one lens plane.  psi_d: (m, m), periodic.  state_d: 12 planes of (npix, npix), npix <= m, in the order
+ * ast_ray_step: one lens plane.  psi_d: (m, m), periodic.  state_d: 12 planes of (npix, npix), npix <= m and
+ *   npix <= 4 * 65535 = 262140 (the launch has one row of workgroups per 4 rows of rays, at most 65535), in the order
  *   d1 d2 s1 s2 A11 A12 A21 A22 B11 B12 B21 B22 (d = beta - theta, s = dx/dchi - theta, A = d beta / d theta - I,
  *   B = d (dx/dchi) / d theta - I; component 1 is array axis 0), updated in place.  Ray (i, j) passes node (i, j) of psi
  *   undeflected.  With dchi = chi_k - chi_prev (formed on the host), 0 <= chi_prev < chi_k:

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from tests import dirty_memory as dm
-from tests import plane_paint_oracle as porc, ray_trace_oracle as orc
+from tests import plane_paint_oracle as porc, ray_trace_cases as cases, ray_trace_oracle as orc
 from tests import stream_order as so
 
 torch = pytest.importorskip("torch")
@@ -49,26 +49,7 @@ def same_bits(got, want):
 
 
 # ------------------------------------------------------------------ (1) step and emit, byte for byte
-def preset_state(npix, m, h, seed):
-    """A random state whose first rows are set so that, after the advance from chi 512 to 1024 (d <- (d + s) / 2,
-    exact), rays land exactly on nodes, at negative positions and beyond the seam of the m-grid."""
-    rng = np.random.default_rng(seed)
-    st = np.empty((12, npix, npix))
-    st[:4] = rng.normal(0.0, 1.5 * h, size=(4, npix, npix))
-    st[4:] = rng.normal(0.0, 0.2, size=(8, npix, npix))
-    st[2:4, :4] = 0.0
-    st[0, 0], st[1, 0] = 2 * -2.5 * h, 2 * 1.25 * h                     # p1 = 0 - 2.5: node -3, wraps to m - 3
-    st[0, 1], st[1, 1] = 2 * 2.0 * h, 2 * -3.0 * h                      # whole pixels: f = 0 on both axes
-    st[0, 2], st[1, 2] = 2 * (m - 2 + 0.75) * h, 2 * (m + 0.5) * h      # p1 = 2 + m - 1.25, p2 = j + m + 0.5: past the seam
-    st[0, 3], st[1, 3] = 0.0, 2 * -(npix - 0.0) * h                     # p2 = j - npix: negative whole pixels
-    return st
-
-
-def landing(st, h, chi_prev, chi_k):
-    d1 = (chi_prev * st[0] + (chi_k - chi_prev) * st[2]) / chi_k
-    d2 = (chi_prev * st[1] + (chi_k - chi_prev) * st[3]) / chi_k
-    n = st.shape[1]
-    return np.arange(n)[:, None] + d1 / h, np.arange(n)[None, :] + d2 / h
+preset_state, landing = cases.preset_state, cases.landing          # shared with the host build's test
 
 
 @pytest.mark.parametrize("born", [False, True], ids=["full", "born"])
@@ -336,3 +317,222 @@ def test_trace_on_dirty_memory_and_behind_a_late_producer(rt):
     torch.cuda.synchronize()
     assert armed, "the trace waited for the device: it must only queue work on the caller's stream"
     assert same_bits(got, want), "behind the late producer"
+
+
+# ------------------------------------------------------------------ many workgroups, second trips, the smallest grids
+SENTINEL = -7.0e77                                          # finite, so that == compares it; no result comes near it
+
+
+def guarded(shape, front=1, behind=4096):
+    """A dense float64 view of ``shape`` inside a flat buffer of SENTINEL, ``front`` elements in: with the default front
+    it starts 8 bytes off a 16-byte boundary.  Returns the view and the two guards."""
+    n = int(np.prod(shape))
+    flat = torch.full((front + n + behind,), SENTINEL, dtype=torch.float64, device="cuda")
+    view = flat[front:front + n].view(*shape)
+    assert view.is_contiguous() and view.data_ptr() == flat.data_ptr() + 8 * front
+    return view, (flat[:front], flat[front + n:])
+
+
+def intact(guards):
+    return all(bool((g == SENTINEL).all()) for g in guards)
+
+
+@pytest.mark.parametrize("born", [False, True], ids=["full", "born"])
+@pytest.mark.parametrize("npix,m", cases.GEOMETRY_SHAPES)
+def test_every_workgroup_of_the_step_equals_the_oracle(rt, npix, m, born):
+    """More than one workgroup along x, partial wavefronts at the x tail, up to 33 rows of workgroups: in every workgroup
+    column and row rays land between nodes, on nodes, below 0 and at or beyond m (asserted on the landing positions)."""
+    h, chi = cases.H, cases.CHI
+    st = cases.geometry_state(npix, m, h, chi[0], chi[1], 200 + npix)
+    assert cases.landing_classes(*landing(st, h, chi[0], chi[1]), m) == []
+    psi1, psi2 = cases.random_psi(m, h, 300 + m), cases.random_psi(m, h, 301 + m)
+    want1 = orc.step(psi1, st, h, chi[0], chi[1], born)
+    want2 = orc.step(psi2, want1, h, chi[1], chi[2], born)
+    assert np.isfinite(want2).all()
+    state = up(st)
+    rt.ray_step(up(psi1), state, h, chi[0], chi[1], born)
+    assert same_bits(state, want1)
+    rt.ray_step(up(psi2), state, h, chi[1], chi[2], born)
+    assert same_bits(state, want2)
+    assert same_bits(rt.ray_emit(state, chi[2], chi[3]), orc.emit(want2, chi[2], chi[3]))
+
+
+@pytest.mark.parametrize("born", [False, True], ids=["full", "born"])
+@pytest.mark.parametrize("npix,m", [(65, 65), (67, 134)])
+def test_step_and_emit_write_nothing_but_their_results(rt, npix, m, born):
+    """The state 8 bytes off a 16-byte boundary with a guard element in front and 4096 behind, the maps in the middle
+    column of a guarded (6, 3, npix, npix) tensor: the guards and the other columns keep the sentinel's bytes."""
+    h, chi = cases.H, cases.CHI
+    st = cases.geometry_state(npix, m, h, chi[0], chi[1], 200 + npix)
+    psi = cases.random_psi(m, h, 300 + m)
+    want = orc.step(psi, st, h, chi[0], chi[1], born)
+    state, guards = guarded((12, npix, npix))
+    assert state.data_ptr() % 16 == 8
+    state.copy_(up(st))
+    rt.ray_step(up(psi), state, h, chi[0], chi[1], born)
+    assert same_bits(state, want) and intact(guards)
+    wide, wide_guards = guarded((6, 3, npix, npix))
+    rt.ray_emit(state, chi[1], chi[2], out=wide[:, 1])
+    assert same_bits(wide[:, 1].contiguous(), orc.emit(want, chi[1], chi[2]))
+    assert bool((wide[:, [0, 2]] == SENTINEL).all()) and intact(wide_guards) and intact(guards)
+    assert same_bits(state, want)
+
+
+def test_the_grid_stride_loops_take_a_second_trip(rt):
+    """npix = 768: 589 824 rays, more than the 2048 x 256 work items of one trip of the emit's loop; the step's 12 x 192
+    workgroups beside it."""
+    npix = m = 768
+    h, chi = cases.H, cases.CHI
+    assert npix * npix > 2048 * 256
+    st = cases.reference_state(npix, m, h, 17)
+    psi = cases.random_psi(m, h, 18)
+    want = orc.step(psi, st, h, chi[0], chi[1])
+    state = up(st)
+    rt.ray_step(up(psi), state, h, chi[0], chi[1])
+    assert same_bits(state, want)
+    maps = orc.emit(want, chi[1], chi[2])
+    assert same_bits(rt.ray_emit(state, chi[1], chi[2]), maps)
+    wide, guards = guarded((6, 2, npix, npix), front=2)
+    rt.ray_emit(state, chi[1], chi[2], out=wide[:, 1])
+    assert same_bits(wide[:, 1].contiguous(), maps) and bool((wide[:, 0] == SENTINEL).all()) and intact(guards)
+
+
+@pytest.mark.parametrize("m", [1100, 1101])
+def test_green_multiply_mode_by_mode_beyond_one_trip(rt, hip, m):
+    """m (m/2 + 1) > 2048 x 256, so the loop of the multiply goes round again.  A spectrum of 1 - 2i everywhere comes
+    back as g (1 - 2i): mode 0 exactly 0, every other mode within max(4 r0, 16 eps) of ``orc.green`` RELATIVELY (the
+    high-k modes are 10^6 times smaller than the low ones), r0 being the oracle's own worst relative distance from a
+    longdouble evaluation.  Measured: r0 = 1.52e-13 (m = 1100) and 1.28e-13 (1101), at the modes (m - 1, 0), where a / m
+    is rounded next to 1 and the sine is pi (1 - a / m); the device, which rounds a / m the same way, is 1.03e-13 and
+    9.8e-14 off the oracle (1.09e-13 and 3.0e-14 off the longdouble value); the bounds are 6.1e-13 and 5.1e-13."""
+    from tests import ray_trace_reference as ref
+    assert np.finfo(np.longdouble).eps <= 2.0 ** -63
+    nh, scale = m // 2 + 1, 0.37
+    assert m * nh > 2048 * 256
+    want, exact = orc.green(m, scale), ref.green(m, scale)
+    nonzero = np.ones((m, nh), dtype=bool)
+    nonzero[0, 0] = False
+    r0 = float((np.abs(want - exact)[nonzero] / np.abs(exact)[nonzero]).max())
+    bound = max(4 * r0, 16 * np.finfo(np.float64).eps)
+    flat = torch.full((m * nh + 4096,), SENTINEL, dtype=torch.complex128, device="cuda")
+    spec = flat[:m * nh].view(m, nh)
+    spec.fill_(complex(1.0, -2.0))
+    assert hip.ast_lens_green_multiply(spec.data_ptr(), m, scale, torch.cuda.current_stream().cuda_stream) == 0
+    got = host(spec)
+    assert got[0, 0] == 0 and bool((flat[m * nh:] == complex(SENTINEL, 0.0)).all())
+    assert np.array_equal(got.imag, -2.0 * got.real)
+    dev = float((np.abs(got.real - want)[nonzero] / np.abs(want)[nonzero]).max())
+    true = float((np.abs(got.real - exact)[nonzero] / np.abs(exact)[nonzero]).max())
+    print(f"m {m}: orc.green is {r0:.2e} off longdouble (worst mode, relative); the device {dev:.2e} off orc.green and "
+          f"{true:.2e} off longdouble; bound {bound:.2e}")
+    assert dev <= bound
+
+
+@pytest.mark.parametrize("npix,pad", [(1024, 1), (520, 2)])
+def test_the_potential_beyond_one_trip_of_the_multiply(rt, npix, pad):
+    """``lens_potential`` at m = 1024 and 1040, where ``ast_lens_green_multiply`` loops: the two assertions of
+    test_the_device_potential_has_the_laplacian_it_was_solved_for, with its tolerances."""
+    rng = np.random.default_rng(40 + npix)
+    sigma = rng.normal(0.0, 40.0, size=(npix, npix))
+    h = math.radians(3.0) / npix
+    m = pad * npix
+    assert m * (m // 2 + 1) > 2048 * 256
+    psi = host(rt.lens_potential(up(sigma), h, pad, 1.0))
+    ref, grid = orc.potential(sigma, h, pad, 1.0)
+    err = np.abs(orc.laplacian(psi, h) - 2.0 * (grid - grid.mean())).max() / np.abs(sigma).max()
+    print(f"npix {npix} pad {pad}: laplacian identity off by {err:.2e} of max |sigma|")
+    assert err <= 1e-12
+    assert np.abs(psi - ref).max() <= 1e-12 * np.abs(ref).max()
+
+
+@pytest.mark.parametrize("born", [False, True], ids=["full", "born"])
+def test_the_smallest_grids_equal_the_oracle(rt, born):
+    """Every 1 <= npix <= m <= 4, where the 4 x 4 stencil wraps onto itself, with displacements of several m."""
+    h = cases.H
+    for npix, m in cases.TINY_SHAPES:
+        psi, st = cases.random_psi(m, h, 70 + m), cases.tiny_state(npix, m, h, 80 + 4 * m + npix)
+        p1, p2 = landing(st, h, 512.0, 1024.0)
+        assert p1[0, 0] == 2 * m and p2[0, 0] == -3 * m
+        want = orc.step(psi, st, h, 512.0, 1024.0, born)
+        state = up(st)
+        rt.ray_step(up(psi), state, h, 512.0, 1024.0, born)
+        assert same_bits(state, want), (npix, m)
+        psi2 = cases.random_psi(m, h, 90 + m)
+        want2 = orc.step(psi2, want, h, 1024.0, 1711.3, born)
+        rt.ray_step(up(psi2), state, h, 1024.0, 1711.3, born)
+        assert same_bits(state, want2), (npix, m)
+        assert same_bits(rt.ray_emit(state, 1711.3, 2950.7), orc.emit(want2, 1711.3, 2950.7)), (npix, m)
+
+
+@pytest.mark.parametrize("npix,pad", [(1, 1), (2, 1), (3, 1), (2, 2), (4, 1), (3, 2)])
+def test_the_potential_of_the_smallest_grids(rt, npix, pad):
+    """m = 1, 2, 3, 4, 6.  ``ast_fft_plan_create`` takes any length >= 1 and the transforms of one element run: one
+    periodic pixel less its mean is 0 everywhere, and so is its potential."""
+    rng = np.random.default_rng(60 + npix)
+    sigma = rng.normal(0.0, 40.0, size=(npix, npix))
+    h, m = math.radians(3.0) / 4, pad * npix
+    psi = host(rt.lens_potential(up(sigma), h, pad, 1.0))
+    ref, grid = orc.potential(sigma, h, pad, 1.0)
+    assert psi.shape == (m, m)
+    if m == 1:
+        assert ref[0, 0] == 0.0 and psi[0, 0] == 0.0
+        return
+    assert np.abs(ref).max() > 0
+    assert np.abs(orc.laplacian(psi, h) - 2.0 * (grid - grid.mean())).max() <= 1e-12 * np.abs(sigma).max()
+    assert np.abs(psi - ref).max() <= 1e-12 * np.abs(ref).max()
+
+
+def test_layouts_of_the_potential_and_the_planes(rt):
+    """psi as a transposed view and 8 bytes into a larger buffer, planes out of a strided stack: the dense call's bytes."""
+    npix, m, h, chi = 24, 48, cases.H, cases.CHI
+    psi, st = cases.random_psi(m, h, 31), cases.reference_state(npix, m, h, 32)
+    want = orc.step(psi, st, h, chi[0], chi[1])
+    turned = up(psi.T).t()
+    assert not turned.is_contiguous() and same_bits(turned.contiguous(), psi)
+    shifted, guards = guarded((m, m))
+    shifted.copy_(up(psi))
+    assert shifted.data_ptr() % 16 == 8
+    for view in (turned, shifted):
+        state = up(st)
+        rt.ray_step(view, state, h, chi[0], chi[1])
+        assert same_bits(state, want)
+    assert intact(guards) and same_bits(shifted, psi)
+    rng = np.random.default_rng(33)
+    stack = up(rng.normal(0.0, 40.0, size=(3, 2 * npix, 2 * npix)))
+    planes = stack[:, ::2, ::2]
+    assert not planes.is_contiguous() and not planes[1].is_contiguous()
+    dist, w = np.array([250.0, 610.0, 1400.0]), orc.plane_weights(1.0 / (1.0 + np.array([0.09, 0.22, 0.55])), OMEGA_M)
+    for pad in (1, 2):
+        dense = rt.trace(planes.contiguous(), dist, w, h, [2300.0, 900.0], pad=pad)
+        assert float(dense.abs().max()) > 0
+        assert same_bits(rt.trace(planes, dist, w, h, [2300.0, 900.0], pad=pad), host(dense))
+
+
+def test_refusals_launch_nothing_and_leave_the_entries_usable(rt, hip):
+    """npix = 262141 .. 262144 would need more than 65535 rows of workgroups; h = 1e-170 has h h = 0.  Both are refused by
+    the argument checks, which come before any access (the pointers are those of a 16-ray state), and the next valid
+    call is the oracle's."""
+    from astrild_amd import _lib
+    npix, m, h = 4, 8, cases.H
+    psi_h, st = cases.random_psi(m, h, 51), cases.tiny_state(npix, m, h, 52)
+    want = orc.step(psi_h, st, h, 512.0, 1024.0)
+    psi, state = up(psi_h), up(st)
+    s = torch.cuda.current_stream().cuda_stream
+
+    def valid_call_still_works():
+        again = up(st)
+        rt.ray_step(psi, again, h, 512.0, 1024.0)
+        assert same_bits(again, want) and same_bits(state, st) and same_bits(psi, psi_h)
+    assert rt.NPIX_MAX == 262140
+    for big in (262141, 262142, 262143, 262144):
+        assert hip.ast_ray_step(psi.data_ptr(), 262144, state.data_ptr(), big, h, 512.0, 1024.0, 0, s) != 0
+        assert b"RAY_BY <= 65535" in hip.ast_last_error()
+        valid_call_still_works()
+    with pytest.raises(ValueError, match="262140"):
+        rt.ray_state(262141)
+    assert hip.ast_ray_step(psi.data_ptr(), m, state.data_ptr(), npix, 1e-170, 512.0, 1024.0, 0, s) != 0
+    assert b"h * h > 0.0" in hip.ast_last_error()
+    valid_call_still_works()
+    with pytest.raises(_lib.AstrildHipError, match="ast_ray_step"):
+        rt.ray_step(psi, state, 1e-170, 512.0, 1024.0)
+    valid_call_still_works()

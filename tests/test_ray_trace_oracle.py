@@ -133,3 +133,21 @@ def test_product_helpers_without_a_device():
             rt.check_pad(bad)
     chi = [250.0, 610.0, 1400.0]
     assert [rt.emitting_plane(chi, c) for c in (0.0, 250.0, 250.1, 610.0, 1400.0, 1e4)] == [-1, -1, 0, 0, 1, 2]
+
+
+def test_the_largest_npix_is_the_one_the_step_entry_takes():
+    """``ast_ray_step`` refuses ``(npix + RAY_BY - 1) / RAY_BY > 65535`` rows of workgroups; ``NPIX_MAX`` is the largest
+    npix that passes, read from the source, and ``ray_state`` refuses the next one before it allocates (no device here)."""
+    import os
+    import re
+    pytest.importorskip("torch")
+    from astrild_amd import ray_trace as rt
+    src = open(os.path.join(os.path.dirname(os.path.abspath(rt.__file__)), "csrc", "ray_trace.hip")).read()
+    rows = int(re.search(r"constexpr int RAY_BX = \d+, RAY_BY = (\d+);", src).group(1))
+    most = int(re.search(r"AST_CHECK_ARG\(\(npix \+ RAY_BY - 1\) / RAY_BY <= (\d+)\);", src).group(1))
+    assert (rows, most) == (4, 65535)
+    assert (rt.NPIX_MAX + rows - 1) // rows <= most < (rt.NPIX_MAX + 1 + rows - 1) // rows
+    assert rt.NPIX_MAX == 4 * 65535 == 262140
+    for bad in (rt.NPIX_MAX + 1, 1 << 18, 0, -1):
+        with pytest.raises(ValueError, match="npix must lie in 1 .. 262140"):
+            rt.ray_state(bad)
